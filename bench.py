@@ -10,6 +10,9 @@ One "step" = one pass of the full evaluation path
 (BASELINE.json configs[1]: "Matterport3D eval, batch 32 pairs @ 640x480, 1xMI355X"), inputs resident in HBM.
 Pairs are independent: ranks shard them with no data-path collective ("weak" scaling); the only collective is
 the MAX over ranks of the timed region.  Rank 0 prints ONE JSON line.
+A plain run of the headline workload sets up, warms up, times --steps steps and prints the line (plus the outputs of the last
+timed step with --dump-outputs DIR); everything else it can measure -- host time per step, pose errors, isolated kernel timings
+and the roofline, the 16-bit modes, the CPU baseline, the legs of the other workloads -- runs with --full.
 """
 import argparse
 import json
@@ -53,6 +56,14 @@ def parse():
                          "ransac.py:151-157)")
     ap.add_argument('--precision', default='fp32', choices=['fp32', 'fp16-fine', 'fp16', 'mixed16'],
                     help='backbone convolution arithmetic (far_amd.loftr.LoFTR.set_precision): fp32 = split-fp16 operand pairs (fp32-grade)')
+    ap.add_argument('--full', action='store_true',
+                    help='headline workload: also measure what its figure does not need -- host time per step, match statistics and pose '
+                         'errors, isolated kernel timings / roofline, other_modes, cpu_baseline, other_workloads (the --no-* / '
+                         '--skip-rooflines options below leave parts of it out).  Default: set up, warm up, time --steps steps, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='headline workload: write what the last timed step returned to its caller (every numeric array test_step adds '
+                         'to the batch) as DIR/<name>.npy, float64 (float64 / integer / bool arrays) or float32; arrays above 4 MiB as a '
+                         'fixed seeded sample of their elements, at most 64 MiB in all (DIR/manifest.json); rank 0 only')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--skip-rooflines', action='store_true',
                     help='c2 child legs of other_workloads only: no isolated kernel timings / roofline object (the parent line carries them)')
@@ -392,7 +403,7 @@ def other_workloads(a):
             ('c2_five_point_solver', ['--minimal', '5', '--steps', '10', '--warmup', '3', '--skip-rooflines'])]
     out = {}
     for name, args in legs:
-        cmd = [sys.executable, os.path.abspath(__file__)] + args + ['--hyp', str(a.hyp), '--no-cpu-baseline', '--no-other-modes',
+        cmd = [sys.executable, os.path.abspath(__file__)] + args + ['--hyp', str(a.hyp), '--full', '--no-cpu-baseline', '--no-other-modes',
                                                                   '--no-other-workloads']
         t0 = time.perf_counter()
         try:
@@ -851,6 +862,53 @@ def bench_c5(a, dev, world, rank, dist):
         dist.destroy_process_group()
 
 
+DUMP_WHOLE_BYTES = 4 << 20      # --dump-outputs: arrays up to this size (as written) are written whole ...
+DUMP_SAMPLE = 1 << 18           # ... larger ones as this many elements at seeded flat indices
+DUMP_LIMIT_BYTES = 64 << 20     # all files together
+
+
+def dump_outputs(batch, inputs, out_dir):
+    """--dump-outputs: every numeric array of `batch` that is not one of the caller's `inputs` (keys starting with '_' are the library's
+    private state) as out_dir/<key>.npy -- float64 for float64 / integer / bool arrays (exact), float32 for the other float types.
+    An array larger than DUMP_WHOLE_BYTES is written as DUMP_SAMPLE of its elements in row-major order, at the indices
+    sorted(numpy.random.default_rng(0).choice(numel, DUMP_SAMPLE, replace=False)): the same indices for the same shape in every run.
+    out_dir/manifest.json lists shape, source dtype and sampling of each file.  Keys are visited in sorted order and the files never
+    exceed DUMP_LIMIT_BYTES together (an array that would pass the limit is sampled down to what is left)."""
+    import re
+    os.makedirs(out_dir, exist_ok=True)
+    manifest, written = {}, 4096                 # (headroom for the .npy headers and the manifest)
+    for key in sorted(batch):
+        v = batch[key]
+        if key in inputs or key.startswith('_'):
+            continue
+        if isinstance(v, np.ndarray) and v.dtype.kind in 'biuf':
+            v = torch.from_numpy(v)
+        if not torch.is_tensor(v) or v.is_complex():
+            continue
+        src = str(v.dtype).replace('torch.', '')
+        wide = v.dtype == torch.float64 or not v.is_floating_point()
+        out = torch.float64 if wide else torch.float32
+        isz = 8 if wide else 4
+        flat = v.detach().reshape(-1)
+        n = flat.numel()
+        k = n if n * isz <= DUMP_WHOLE_BYTES else DUMP_SAMPLE
+        k = min(k, max(0, (DUMP_LIMIT_BYTES - written - 256) // isz))
+        ent = {'shape': list(v.shape), 'dtype': src, 'written': str(out).replace('torch.', '')}
+        if k < n:
+            idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            ent['sampled'] = {'elements': k, 'indices': 'sorted(numpy.random.default_rng(0).choice(numel, elements, replace=False))'}
+            arr = flat.to(out).cpu().numpy()
+        else:
+            arr = flat.to(out).cpu().numpy().reshape(tuple(v.shape))
+        np.save(os.path.join(out_dir, re.sub(r'[^A-Za-z0-9_.-]', '_', key) + '.npy'), arr)
+        written += arr.nbytes + 256
+        manifest[key] = ent
+    with open(os.path.join(out_dir, 'manifest.json'), 'w') as f:
+        json.dump(manifest, f, indent=1)
+    return manifest
+
+
 def main():
     a = parse()
     if a.pairs is None:
@@ -928,12 +986,12 @@ def main():
         last = step()
     fence()
     dt = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:                      # before any other step runs: the library reuses its buffers from step to step
+        dump_outputs(last, base, a.dump_outputs)
     from far_amd import parallel
     per_rank_ms = [round(1000 * x / a.steps, 3) for x in parallel.gather_floats(dt, device=dev)]
-    per_rank_host_ms = [round(x, 3) for x in parallel.gather_floats(host_work_ms(step), device=dev)]
+    per_rank_host_ms = [round(x, 3) for x in parallel.gather_floats(host_work_ms(step), device=dev)] if a.full else None
     dt = parallel.max_over_ranks(dt, device=dev)          # the slowest rank defines the step time
-    matches = float(last['b_ids'].numel()) / a.pairs
-    ok_frac = float(last['solver_status'].float().mean().item())
     # pose error of the solver and of the blended head output against the synthetic ground truth
     # (pure lateral translation, no rotation): informational -- the banded synthetic pairs carry the usual
     # small-baseline translation/rotation ambiguity; accuracy on Matterport needs the real checkpoint + data.
@@ -950,17 +1008,20 @@ def main():
         te2, Re2, _ = fm.relative_pose_error_batch(T_gt.cpu(), Rr, tr)
         return {'solver_median_R_deg': round(float(Re.median()), 3), 'solver_median_t_deg': round(float(te.median()), 3),
                 'head_median_R_deg': round(float(Re2.median()), 3), 'head_median_t_deg': round(float(te2.median()), 3)}
-    pose_err = dict(pose_errors(last), note='vs synthetic GT (R=I, t=-x); random-weight head; Matterport accuracy pending (no ckpt/data offline)')
+    if a.full:
+        matches = float(last['b_ids'].numel()) / a.pairs
+        ok_frac = float(last['solver_status'].float().mean().item())
+        pose_err = dict(pose_errors(last), note='vs synthetic GT (R=I, t=-x); random-weight head; Matterport accuracy pending (no ckpt/data offline)')
 
     # N > 1: the dense-f16 MFMA rate every rank sustains right now (far_mfma_probe_f16 on all ranks at once): under one node's
     # power envelope a sub-linear scaling curve can then be told apart from ranks that simply clock lower together
     per_rank_peak = None
-    if world > 1:
+    if world > 1 and a.full:
         pk = max(v['tflops'] for v in mfma_sustained_peak().values())
         per_rank_peak = [round(x, 1) for x in parallel.gather_floats(pk, device=dev)]
     if rank == 0:
         kr, roof = {}, None
-        if not a.skip_rooflines:
+        if a.full and not a.skip_rooflines:
             kr = kernel_rooflines(a.pairs)
             # dominant kernel of the step: the backbone's 3x3 convolutions (45 % of the kernel-busy time, profiles/); its costliest launch
             # is reported -- K17 (Winograd) since round 4, K9 (direct) when ops.USE_WINO is off
@@ -1010,12 +1071,6 @@ def main():
             'value': round(world * a.pairs * a.steps / dt, 3), 'unit': 'image-pairs/sec',
             'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'prime_steps': prime, 'prime_cap': max(0, 3 - a.warmup) + a.warmup + SETTLE_EXTRA,
             'ms_per_step': round(1000 * dt / a.steps, 3), 'per_rank_ms_per_step': per_rank_ms,
-            # host time of a step without its waits for the GPU (host_work_ms: Python + ctypes + the caching allocator), measured on
-            # three extra untimed steps: what N ranks on one host contend for
-            'host_ms_per_step': max(per_rank_host_ms), 'per_rank_host_ms_per_step': per_rank_host_ms,
-            # normal hosts: ~5 ms.  A box whose host is an order of magnitude slower (seen once in ~15 runs of round 6: 42.9 ms, step 113.5 ms
-            # with unchanged kernels) cannot keep the GPU fed behind the step's match-count read: the line then measures the host
-            'host_bound': bool(max(per_rank_host_ms) > 0.2 * 1000 * dt / a.steps),
             'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': 'f32' if a.precision == 'fp32' else f'f32 tensors/accumulation, {a.precision} matrix operands',
             'dtype_note': ('f32 = fp32 tensors, fp32 accumulation; matrix products on the f16 MFMA pipe as split-f16x3 operand '
@@ -1030,14 +1085,22 @@ def main():
                                    'step, the second call re-runs only the 13-number-dependent MLPs / gate on it; exact reuse, '
                                    'tests/test_pipeline_gpu.py), seeded random weights',
                        'pairs_per_gpu': a.pairs, 'hypotheses': a.hyp, 'minimal_solver': a.minimal, 'fine_pred_steps': 2,
-                       'matches_per_pair': round(matches, 1), 'solver_success_frac': ok_frac, 'pose_error': pose_err,
                        'parallelism': f'dp{world} (independent pairs, no data-path collective)'},
             'roofline': roof,
             'kernels': {k: {kk: round(vv, 4) for kk, vv in v.items()} for k, v in kr.items()},
             'build_id': _build_id(),
             'process_group': {'backend': dist.get_backend(), 'world_size': dist.get_world_size()} if dist is not None else None,
         }
-        if world == 1 and a.precision == 'fp32' and not a.no_other_modes:
+        if a.full:
+            res.update({
+                # host time of a step without its waits for the GPU (host_work_ms: Python + ctypes + the caching allocator), measured on
+                # three extra untimed steps: what N ranks on one host contend for
+                'host_ms_per_step': max(per_rank_host_ms), 'per_rank_host_ms_per_step': per_rank_host_ms,
+                # normal hosts: ~5 ms.  A box whose host is an order of magnitude slower (seen once in ~15 runs of round 6: 42.9 ms, step 113.5 ms
+                # with unchanged kernels) cannot keep the GPU fed behind the step's match-count read: the line then measures the host
+                'host_bound': bool(max(per_rank_host_ms) > 0.2 * 1000 * dt / a.steps)})
+            res['config'].update({'matches_per_pair': round(matches, 1), 'solver_success_frac': ok_frac, 'pose_error': pose_err})
+        if a.full and world == 1 and a.precision == 'fp32' and not a.no_other_modes:
             # INFORMATIONAL, never `value`: the same step with 16-bit matrix operands in some or all stages (LoFTR.set_precision).  The
             # reference computes in fp32 throughout (no autocast anywhere in it), so the fp32-grade line above is the only parity
             # configuration; every entry below states what it costs: match-set IoU against the parity line (ids are no longer
@@ -1110,11 +1173,11 @@ def main():
                 stages['union_of_stages_within_1.1x'] = entry(dtu, accu, 'stages: ' + ', '.join(union) + ' -- every stage whose own solver rotation error '
                                                                          'stays within 1.1x of the parity line, together')
             res['other_modes']['precision_stages'] = stages
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(a.cpu_pairs, a.hyp)
         if per_rank_peak is not None:
             res['per_rank_sustained_peak'] = per_rank_peak
-        if world == 1 and a.precision == 'fp32' and a.pairs == PAIRS_PER_GPU and not a.no_other_workloads:
+        if a.full and world == 1 and a.precision == 'fp32' and a.pairs == PAIRS_PER_GPU and not a.no_other_workloads:
             res['other_workloads'] = other_workloads(a)
         print(json.dumps(res), flush=True)
     if dist is not None:

@@ -18,7 +18,7 @@ def _run(extra, gpus=2):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(gpus), '--backend', 'gloo', '--share-gpu', '--steps', '1',
-           '--warmup', '1', '--no-cpu-baseline'] + extra
+           '--warmup', '1', '--full', '--no-cpu-baseline'] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -116,7 +116,7 @@ def _run_rccl_world1(extra, launcher):
     for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     args = [os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--backend', 'nccl', '--dist-at-world-1', '--steps', '1', '--warmup', '1',
-            '--no-cpu-baseline', '--no-other-workloads', '--no-other-modes'] + extra
+            '--full', '--no-cpu-baseline', '--no-other-workloads', '--no-other-modes'] + extra
     if launcher:
         from far_amd import parallel
         cmd = parallel.launch_command(1, args)

@@ -1,7 +1,7 @@
-"""Assembles profiles/<tag>_bench_fp32_kernel_trace.txt from the files tools/collect_profiles.sh leaves in gpurun_out/:
+"""Assembles profiles/<tag>_bench_fp32_kernel_trace.txt from the files tools/collect_profiles.sh leaves in its output folder:
   bench_prof.log (bench.py under rocprofv3), <tag>_trace.txt (tools/profile_report.py on the rocpd database),
   bench_plain.log / bench_c4.log (the un-profiled python bench.py lines), and copies <tag>_pmc_traffic.json.
-Usage: python tools/make_profile_txt.py r02 <commit>"""
+Usage: python tools/make_profile_txt.py r02 <commit> [folder, default profile_out/]"""
 import os
 import shutil
 import sys
@@ -9,18 +9,18 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else 'r02'
 commit = sys.argv[2] if len(sys.argv) > 2 else 'unknown'
-G = ROOT + '/gpurun_out/'
+G = os.path.abspath(sys.argv[3] if len(sys.argv) > 3 else os.path.join(ROOT, 'profile_out')) + '/'
 last_json = lambda path: [l for l in open(path).read().splitlines() if l.startswith('{')][-1]
 plain, prof, c4 = last_json(G + 'bench_plain.log'), last_json(G + 'bench_prof.log'), last_json(G + 'bench_c4.log')
 tr = open(G + f'{tag}_trace.txt').read()
 whole, win = tr.split('\n\n', 1)
 rnd = tag[1:].lstrip('0')
-out = f"""# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 3 --no-cpu-baseline --no-other-modes    (round {rnd}, 1x MI355X, default fp32-grade path, commit {commit})
+out = f"""# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 3 --full --no-cpu-baseline --no-other-modes    (round {rnd}, 1x MI355X, default fp32-grade path, commit {commit})
 # collected by tools/collect_profiles.sh; summarised by tools/profile_report.py (rocpd database -> per-kernel tables)
 # bench line of the same profiled run:
 {prof}
 
-# un-profiled bench line (python bench.py: 5 steps after 3 warm-up steps) on the same box:
+# un-profiled bench line (python bench.py --full: 5 steps after 3 warm-up steps) on the same box:
 {plain}
 
 # un-profiled line of the second workload (python bench.py --workload c4: BASELINE configs[3], cached-LoFTR path, batch 256):
@@ -78,7 +78,7 @@ if os.path.exists(G + 'bench_c5.log'):
 if os.path.exists(G + f'{tag}_trace_fp16.txt') and os.path.exists(G + 'bench_fp16_prof.log'):
     trm = open(G + f'{tag}_trace_fp16.txt').read()
     wholem, winm = trm.split('\n\n', 1)
-    outm = f"""# rocprofv3 --kernel-trace --stats -- python3 bench.py --precision fp16 --steps 3 --warmup 3 --no-cpu-baseline --no-other-modes --no-other-workloads --skip-rooflines    (round {rnd}, 1x MI355X, commit {commit})
+    outm = f"""# rocprofv3 --kernel-trace --stats -- python3 bench.py --precision fp16 --steps 3 --warmup 3 --full --no-cpu-baseline --no-other-modes --no-other-workloads --skip-rooflines    (round {rnd}, 1x MI355X, commit {commit})
 # the 16-bit-operand class BASELINE configs[1] names: plain fp16 operands in K9 (backbone, encoder layers), K13 / K14 and K2, bf16 in K1;
 # fp32 tensors and accumulation.  NOT the parity configuration (match-set IoU ~0.997 vs it): bench.py reports it under other_modes, never as `value`.
 # bench line of the profiled run:
