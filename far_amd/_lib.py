@@ -38,6 +38,10 @@ SIGNATURES = {
     'far_coarse_match_f16s': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f,
                                     c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
     'far_conf_matrix_f16s': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
+    'far_coarse_match_sinkhorn_f16s_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
+    'far_coarse_match_sinkhorn_f16s': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_f,
+                                             c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                                             c_p, c_p, c_p]),
     'far_coarse_train_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i]),
     'far_coarse_pos_conf_f16s': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p]),
     'far_coarse_pos_conf_bwd_f16': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p]),
@@ -158,7 +162,7 @@ class EncLayer(ctypes.Structure):
                [(n, ctypes.c_void_p) for n in ('g1', 'b1', 'g2', 'b2', 'overflow')]
 
 
-EXPECTED_ABI = 7          # far_abi_version() of the library these signatures describe (include/far_hip.h)
+EXPECTED_ABI = 8          # far_abi_version() of the library these signatures describe (include/far_hip.h)
 _lib = None
 
 

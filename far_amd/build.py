@@ -294,8 +294,13 @@ def partial_write_check(path):
     return n, bad
 
 
+# headers whose device code issues LDS-DMA: a file that includes one is scanned like a file that issues it itself
+LDS_DMA_HEADERS = ('k1_f16s.h',)
+
+
 def uses_lds_dma(src):
-    return 'global_load_lds' in open(src).read()
+    txt = open(src).read()
+    return 'global_load_lds' in txt or any(f'#include "{h}"' in txt for h in LDS_DMA_HEADERS)
 
 
 def uses_split_asm(src):

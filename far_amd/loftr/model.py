@@ -144,6 +144,8 @@ class LoFTR(nn.Module):
             st = set(mode)
             if not st <= set(self.STAGES):
                 raise ValueError(f'unknown precision stages {sorted(st - set(self.STAGES))}; known: {self.STAGES}')
+        if 'k1' in st and getattr(getattr(self, 'coarse_matching', None), 'match_type', None) == 'sinkhorn':
+            raise NotImplementedError("Sinkhorn coarse matching has no 16-bit operand variant: precision stage 'k1' is not available")
         self.precision_stages = tuple(s for s in self.STAGES if s in st)
         if hasattr(self, 'backbone'):                      # (the cached-prediction configuration builds the head only)
             self.backbone.trunk_split = 'trunk' not in st
@@ -444,6 +446,8 @@ class LoFTR(nn.Module):
                 with ops.activation_exponent(self.act_exp):
                     out = fn()
             except ops.ActivationOverflow:
+                if saved is not None:                          # raised by a re-run: the widening did not yield a clean run
+                    self._restore_range_state(saved)
                 raise
             except Exception:
                 self._join_side()

@@ -35,8 +35,14 @@ class CoarseMatching(nn.Module):
         self.train_coarse_percent = config['train_coarse_percent']
         self.train_pad_num_gt_min = config['train_pad_num_gt_min']
         self.match_type = config['match_type']
-        if self.match_type != 'dual_softmax':
-            raise NotImplementedError("only match_type='dual_softmax' (the FAR configuration) has a kernel")
+        if self.match_type == 'sinkhorn':
+            # optimal transport with a learned dustbin score (coarse_matching.py:73-82; the loftr_ot* configurations): inference on
+            # far_coarse_match_sinkhorn_f16s; training through it (backward, dustbin-supervised loss) is not built
+            self.bin_score = nn.Parameter(torch.tensor(config['skh_init_bin_score'], requires_grad=True))
+            self.skh_iters = config['skh_iters']
+            self.skh_prefilter = config['skh_prefilter']
+        elif self.match_type != 'dual_softmax':
+            raise NotImplementedError(f"match_type={self.match_type!r}: only 'dual_softmax' and 'sinkhorn' have kernels")
         self.temperature = config['dsmax_temperature']
         # data['conf_matrix'] (92 MB / pair) is consumed only by the coarse loss and by plotting
         # (loftr_loss.py:307-311); it is materialised when training or when asked for explicitly.
@@ -52,6 +58,8 @@ class CoarseMatching(nn.Module):
         """feat_c0 [N, L, C], feat_c1 [N, S, C]; updates data with conf_matrix (optional), b_ids, i_ids,
         j_ids, gt_mask, m_bids, mkpts0_c, mkpts1_c, mconf (coarse_matching.py:144-147, :243-263).
         overlap (inference on the GPU): see ops.coarse_match -- work enqueued behind K1 while the host waits for the match count."""
+        if self.match_type == 'sinkhorn':
+            return self._forward_sinkhorn(feat_c0, feat_c1, data, mask_c0, mask_c1, overlap)
         if not feat_c0.is_cuda:
             ag.require('CoarseMatching on CPU tensors')
         if self.training or ag.needs_grad(feat_c0, feat_c1):
@@ -91,6 +99,53 @@ class CoarseMatching(nn.Module):
                                                        data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids'], self.temperature)
         else:
             data.pop('conf_pos', None)
+
+    def _valid_hw(self, data):
+        if 'mask0' not in data:
+            return None
+        # mask_border_with_padding (:28-43): per-sample valid extents of the padded coarse masks
+        m0, m1 = data['mask0'], data['mask1']
+        return torch.stack([m0.sum(1).max(-1)[0], m0.sum(-1).max(-1)[0],
+                            m1.sum(1).max(-1)[0], m1.sum(-1).max(-1)[0]], 1).to(torch.int32).contiguous()
+
+    def _forward_sinkhorn(self, feat_c0, feat_c1, data, mask_c0=None, mask_c1=None, overlap=None):
+        """match_type 'sinkhorn' in evaluation mode (coarse_matching.py:120-147): the same data keys as the dual-softmax
+        evaluation path, plus conf_matrix_with_bin when materialize_conf is set (conf_matrix is then its [:, :L, :S] view)."""
+        if self.training or ag.needs_grad(feat_c0, feat_c1):
+            raise NotImplementedError('Sinkhorn coarse matching: training / gradients through the optimal-transport matcher are not '
+                                      'built (inference only)')
+        if not feat_c0.is_cuda:
+            ag.require('Sinkhorn CoarseMatching on CPU tensors')
+        if self.bf16:
+            raise NotImplementedError("Sinkhorn coarse matching has no 16-bit operand variant (set_precision stage 'k1')")
+        if feat_c0.shape[-1] != 256:
+            raise NotImplementedError(f'Sinkhorn coarse matching has a kernel for C = 256 only (got C = {feat_c0.shape[-1]})')
+        # `variant` is not consulted: the activation-range guard sets it to 'f32' whenever ANY split-fp16 launch of the call overflowed,
+        # and there is one Sinkhorn form.  Its operand preparation reports coarse features beyond the split range (|x| > 4094) through
+        # the same device flag as K1's, so an overflow elsewhere is widened and re-run as usual, while coarse features out of range keep
+        # the flag raised at every exponent: the guard then restores the module and raises ActivationOverflow.
+        as_u8 = lambda m: None if m is None else m.to(torch.uint8).contiguous()
+        scale = data['hw0_i'][0] / data['hw0_c'][0]
+        s0 = data['scale0'].float().contiguous() if 'scale0' in data else None
+        s1 = data['scale1'].float().contiguous() if 'scale1' in data else None
+        out = ops.coarse_match_sinkhorn(feat_c0.float().contiguous(), feat_c1.float().contiguous(), self.bin_score, self.skh_iters,
+                                        self.thr, self.border_rm, data['hw0_c'], data['hw1_c'], scale, as_u8(mask_c0),
+                                        as_u8(mask_c1), self._valid_hw(data), s0, s1, prefilter=self.skh_prefilter,
+                                        want_conf=self.materialize_conf, overlap=overlap)
+        mconf = out['mconf']
+        data.update({
+            'conf_matrix': out['conf_matrix'],
+            'b_ids': out['b_ids'], 'i_ids': out['i_ids'], 'j_ids': out['j_ids'],
+            'gt_mask': mconf == 0,
+            'm_bids': out['b_ids'],
+            'mkpts0_c': out['mkpts0_c'], 'mkpts1_c': out['mkpts1_c'], 'mconf': mconf,
+            'match_counts': out['counts'],
+        })
+        if out['conf_matrix_with_bin'] is not None:
+            data['conf_matrix_with_bin'] = out['conf_matrix_with_bin']
+        else:
+            data.pop('conf_matrix_with_bin', None)
+        data.pop('conf_pos', None)          # the validation branch's sparse dual-softmax confidences do not apply
 
     # ------------------------------------------------------------------------------------------------------
     # training (coarse_matching.py:86-147 + :199-240).  The coarse loss of this configuration (dual-softmax, sparse

@@ -76,6 +76,59 @@ def coarse_match(f0, f1, temperature, thr, border, hw0, hw1, cell_scale, mask0=N
         'mkpts0_c': mk0[:M], 'mkpts1_c': mk1[:M], 'counts': counts_h[:Z], 'conf_matrix': conf,
     }
 
+def coarse_match_sinkhorn(f0, f1, bin_score, iters, thr, border, hw0, hw1, cell_scale, mask0=None, mask1=None, valid_hw=None,
+                          scale0=None, scale1=None, prefilter=False, want_conf=False, want_potentials=False, overlap=None):
+    """LoFTR's optimal-transport coarse matcher (match_type 'sinkhorn', coarse_matching.py:120-142) on the split-fp16 operands of K1
+    (far_coarse_match_sinkhorn_f16s); C must be 256.  bin_score: a one-element fp32 tensor on the GPU (the module's Parameter), read
+    by the kernels -- no host copy.  Returns ops.coarse_match's dict plus conf_matrix_with_bin (Z, L+1, S+1), log_u (Z, L+1) and
+    log_v (Z, S+1), each None unless asked for (want_conf / want_potentials); conf_matrix is the [:, :L, :S] view of
+    conf_matrix_with_bin.  Host synchronisation and `overlap` as ops.coarse_match."""
+    lib = _lib.load()
+    Z, L, C = f0.shape
+    S = f1.shape[1]
+    dev = f0.device
+    if not f0.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if C != 256:
+        raise NotImplementedError('the Sinkhorn coarse matcher has a kernel for C = 256 only')
+    ws = _ws(lib.far_coarse_match_sinkhorn_f16s_workspace_bytes(Z, L, S, C), dev)
+    cap = Z * L
+    b_ids = torch.empty(cap, dtype=torch.int64, device=dev)
+    i_ids = torch.empty(cap, dtype=torch.int64, device=dev)
+    j_ids = torch.empty(cap, dtype=torch.int64, device=dev)
+    mconf = torch.empty(cap, dtype=torch.float32, device=dev)
+    mk0 = torch.empty(cap, 2, dtype=torch.float32, device=dev)
+    mk1 = torch.empty(cap, 2, dtype=torch.float32, device=dev)
+    counts = torch.empty(Z + 1, dtype=torch.int32, device=dev)
+    conf = torch.empty(Z, L + 1, S + 1, dtype=torch.float32, device=dev) if want_conf else None
+    log_u = torch.empty(Z, L + 1, dtype=torch.float32, device=dev) if want_potentials else None
+    log_v = torch.empty(Z, S + 1, dtype=torch.float32, device=dev) if want_potentials else None
+    bin_score = bin_score.detach()
+    if bin_score.dtype != torch.float32 or not bin_score.is_contiguous():
+        bin_score = bin_score.float().contiguous()
+    rc = lib.far_coarse_match_sinkhorn_f16s(
+        _p(f0, torch.float32), _p(f1, torch.float32), Z, L, S, C, _p(bin_score, torch.float32), int(iters), int(bool(prefilter)),
+        float(thr), int(border), int(hw0[0]), int(hw0[1]), int(hw1[0]), int(hw1[1]), float(cell_scale),
+        _p(mask0, torch.uint8), _p(mask1, torch.uint8), _p(valid_hw, torch.int32), _p(scale0, torch.float32), _p(scale1, torch.float32),
+        _p(conf), _p(log_u), _p(log_v), _p(b_ids), _p(i_ids), _p(j_ids), _p(mconf), _p(mk0), _p(mk1),
+        _p(counts), ctypes.c_void_p(counts.data_ptr() + 4 * Z), _p(ws), _p(overflow_flag(dev)), _stream())
+    _lib.check(rc, 'far_coarse_match_sinkhorn_f16s')
+    if overlap is None:
+        counts_h = counts.cpu()
+    else:
+        counts_h = torch.empty(Z + 1, dtype=torch.int32, pin_memory=True)
+        counts_h.copy_(counts, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        overlap()
+        done.synchronize()
+    M = int(counts_h[Z])
+    return {
+        'b_ids': b_ids[:M], 'i_ids': i_ids[:M], 'j_ids': j_ids[:M], 'mconf': mconf[:M],
+        'mkpts0_c': mk0[:M], 'mkpts1_c': mk1[:M], 'counts': counts_h[:Z],
+        'conf_matrix': None if conf is None else conf[:, :L, :S], 'conf_matrix_with_bin': conf, 'log_u': log_u, 'log_v': log_v,
+    }
+
 def conf_matrix(f0, f1, temperature, mask0=None, mask1=None, out=None):
     """K1, materialising mode: data['conf_matrix'] (Z, L, S) alone (coarse_matching.py:108-118) at HBM write speed
     (far_conf_matrix_f16s: fp32-grade statistics, plain-fp16 scores, exact recomputation of every entry above 2^-12).

@@ -30,7 +30,7 @@ typedef struct ihipStream_t* far_stream_t; /* == hipStream_t */
 
 /* ABI version of this header; bumped when a signature changes (2: activation exponent / overflow flag of K9, K13, K14; 3: the
  * far_wino_* / far_conv3x3_wino_f32 entry points, 16 tuning keys; 4: far_upsample2x_bwd_f32, far_fine_scatter_det_f32, far_bn_train_*, far_adamw_*; 5: far_linear_kv_f16s, far_linear_q_apply_f16s,
- * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0).  far_amd/_lib.py refuses a library whose version differs. */
+ * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s).  far_amd/_lib.py refuses a library whose version differs. */
 int far_abi_version(void);
 /* Id of the sources the library was built from: sha256/16 over far_amd/csrc/* and the compiler flags (far_amd/build.py
  * source_id()).  far_amd/_lib.py refuses a library whose id differs from the sources it sits next to. */
@@ -129,6 +129,27 @@ int far_coarse_match_f16s(const float* f0, const float* f1, int Z, int L, int S,
 int far_conf_matrix_f16s(const float* f0, const float* f1, int Z, int L, int S, int C, float temperature,
                          const uint8_t* mask0, const uint8_t* mask1, int stages, float* conf_out, int* fix_info_out,
                          void* ws, int* overflow, far_stream_t stream);
+
+/* LoFTR's optimal-transport coarse matcher (match_type 'sinkhorn', coarse_matching.py:120-142; sinkhorn_f16s.hip): log-domain
+ * Sinkhorn with a dustbin row and column on K1's split-fp16 operands, without the (Z, L+1, S+1) coupling matrix, then K1's selection
+ * (threshold, border, mutual nearest neighbour, ordered compaction) on conf_matrix = assign[:, :L, :S].  Arguments as
+ * far_coarse_match_f16s without the temperature (the similarity is <f0, f1> / C), plus:
+ *   bin_score      device float: the dustbin score alpha (LoFTR's coarse_matching.bin_score); read on the device, no host copy
+ *   iters          Sinkhorn iterations T >= 0 (skh_iters)
+ *   prefilter      1: a row / column of conf_matrix whose argmax over assign is its dustbin entry is zeroed before the selection
+ *                  (skh_prefilter, evaluation mode)
+ *   conf_with_bin  optional (Z, L+1, S+1): the whole assignment matrix exp(log_assign), with the prefilter's zeros
+ *   log_u, log_v   optional (Z, L+1), (Z, S+1): the final potentials u, v (natural log)
+ * The overflow flag means what it means for far_coarse_match_f16s; C must be 256. */
+size_t far_coarse_match_sinkhorn_f16s_workspace_bytes(int Z, int L, int S, int C);
+int far_coarse_match_sinkhorn_f16s(const float* f0, const float* f1, int Z, int L, int S, int C,
+                                   const float* bin_score, int iters, int prefilter, float thr, int border,
+                                   int h0, int w0, int h1, int w1, float cell_scale, const uint8_t* mask0, const uint8_t* mask1,
+                                   const int* valid_hw, const float* scale0, const float* scale1,
+                                   float* conf_with_bin, float* log_u, float* log_v,
+                                   int64_t* b_ids, int64_t* i_ids, int64_t* j_ids, float* mconf,
+                                   float* mkpts0_c, float* mkpts1_c, int* counts_out, int* total_out,
+                                   void* ws, int* overflow, far_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * K1 on the training path: sparse coarse supervision without conf_matrix / conf_matrix_gt
