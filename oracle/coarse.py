@@ -1,7 +1,7 @@
 """Oracle for K1: coarse matching (test infrastructure only, see oracle/__init__.py).
 
 Follows mp3d_loftr/src/loftr/utils/coarse_matching.py: CoarseMatching.forward :86-147 (dual_softmax
-branch) and get_coarse_match :149-265 (eval path), mask_border :8-25.
+branch) and get_coarse_match :149-265 (eval path), mask_border :8-25, mask_border_with_padding :28-43.
 """
 import numpy as np
 
@@ -14,7 +14,7 @@ def _softmax(x, axis):
     return e / e.sum(axis=axis, keepdims=True)
 
 
-def conf_matrix(feat_c0, feat_c1, temperature, mask_c0=None, mask_c1=None, dtype=np.float32):
+def conf_matrix(feat_c0, feat_c1, temperature, mask_c0=None, mask_c1=None, dtype=np.float32, keep_input_precision=False):
     """coarse_matching.py:101-118.  feat (N,L,C)/(N,S,C) float32 -> conf (N,L,S).
 
     dtype=float32 follows the reference's arithmetic type.  NOTE (measured, tests/test_oracle_golden.py::test_g1_coarse_full_grid_and_fp32_swamping):
@@ -22,12 +22,15 @@ def conf_matrix(feat_c0, feat_c1, temperature, mask_c0=None, mask_c1=None, dtype
     swamping; the reference's own torch-CPU result (and this function in float32) deviates up to ~7e-5
     from the exact value.  dtype=float64 evaluates the same formulas on the same fp32 inputs without that
     loss and is what kernels are held to tightly; both are compared in the parity tests.
+    keep_input_precision: float64 features stay float64 (oracle.model.matcher_forward's float64 mode, where the tokens themselves
+    are float64 results); the default rounds the inputs to fp32 first, as every kernel-level caller expects.
     """
-    feat_c0 = np.asarray(feat_c0, np.float32)
-    feat_c1 = np.asarray(feat_c1, np.float32)
+    if not (keep_input_precision and dtype == np.float64):
+        feat_c0 = np.asarray(feat_c0, np.float32)
+        feat_c1 = np.asarray(feat_c1, np.float32)
     C = feat_c0.shape[-1]
-    f0 = (feat_c0 / np.float32(C ** .5)).astype(dtype)                   # :104-105
-    f1 = (feat_c1 / np.float32(C ** .5)).astype(dtype)
+    f0 = (feat_c0 / feat_c0.dtype.type(C ** .5)).astype(dtype)           # :104-105
+    f1 = (feat_c1 / feat_c1.dtype.type(C ** .5)).astype(dtype)
     sim = np.matmul(f0, np.swapaxes(f1, 1, 2)) / dtype(np.float32(temperature))  # :108-109 (einsum nlc,nsc->nls)
     if mask_c0 is not None:                                               # :110-113
         valid = mask_c0[..., None].astype(bool) & mask_c1[:, None].astype(bool)
@@ -49,14 +52,40 @@ def mask_border(m, b, v):
     m[:, :, :, :, -b:] = v
 
 
-def get_coarse_match(conf, thr, border_rm, hw0_c, hw1_c, hw0_i, scale0=None, scale1=None):
-    """coarse_matching.py:149-265, eval path (self.training False, no padded masks)."""
+def valid_extents(mask0, mask1):
+    """coarse_matching.py:37-38: per pair (h0, w0, h1, w1), the largest column sum / row sum of each padded mask (N, h, w)."""
+    m0, m1 = np.asarray(mask0).astype(np.int64), np.asarray(mask1).astype(np.int64)
+    return np.stack([m0.sum(1).max(-1), m0.sum(-1).max(-1), m1.sum(1).max(-1), m1.sum(-1).max(-1)], 1)
+
+
+def mask_border_with_padding(m, b, v, mask0, mask1):
+    """coarse_matching.py:28-43, m: (N,H0,W0,H1,W1) bool, in place: the near border as mask_border, the far border from each
+    pair's valid extents (everything from extent - b on, which takes the padding with it)."""
+    if b <= 0:
+        return
+    m[:, :b] = v
+    m[:, :, :b] = v
+    m[:, :, :, :b] = v
+    m[:, :, :, :, :b] = v
+    for n, (h0, w0, h1, w1) in enumerate(valid_extents(mask0, mask1)):    # :39-43
+        m[n, h0 - b:] = v
+        m[n, :, w0 - b:] = v
+        m[n, :, :, h1 - b:] = v
+        m[n, :, :, :, w1 - b:] = v
+
+
+def get_coarse_match(conf, thr, border_rm, hw0_c, hw1_c, hw0_i, scale0=None, scale1=None, mask0=None, mask1=None):
+    """coarse_matching.py:149-265, eval path (self.training False).  mask0 / mask1 (N, h, w): the padded coarse masks of the data
+    dict; with them the far border follows each pair's valid extents (:179-181)."""
     N, L, S = conf.shape
     h0, w0 = hw0_c
     h1, w1 = hw1_c
     mask = conf > np.float32(thr)                                         # :174
     mask = mask.reshape(N, h0, w0, h1, w1).copy()                         # :175-176
-    mask_border(mask, border_rm, False)                                   # :178
+    if mask0 is None:
+        mask_border(mask, border_rm, False)                               # :177-178
+    else:
+        mask_border_with_padding(mask, border_rm, False, mask0, mask1)    # :179-181
     mask = mask.reshape(N, L, S)                                          # :182-183
     mask = mask & (conf == conf.max(axis=2, keepdims=True)) \
                 & (conf == conf.max(axis=1, keepdims=True))               # :186-188
@@ -79,9 +108,11 @@ def get_coarse_match(conf, thr, border_rm, hw0_c, hw1_c, hw0_i, scale0=None, sca
 
 
 def coarse_matching(feat_c0, feat_c1, cfg, hw0_c, hw1_c, hw0_i, mask_c0=None, mask_c1=None,
-                    scale0=None, scale1=None, dtype=np.float32):
-    conf = conf_matrix(feat_c0, feat_c1, cfg['dsmax_temperature'], mask_c0, mask_c1, dtype)
-    out = get_coarse_match(conf, cfg['thr'], cfg['border_rm'], hw0_c, hw1_c, hw0_i, scale0, scale1)
+                    scale0=None, scale1=None, dtype=np.float32, mask0=None, mask1=None, keep_input_precision=False):
+    """mask_c0 (N, L) / mask_c1 (N, S): the flattened masks of the similarity fill; mask0 / mask1 (N, h, w): the same masks on
+    their grids, for the far border (the reference reads them from the data dict)."""
+    conf = conf_matrix(feat_c0, feat_c1, cfg['dsmax_temperature'], mask_c0, mask_c1, dtype, keep_input_precision)
+    out = get_coarse_match(conf, cfg['thr'], cfg['border_rm'], hw0_c, hw1_c, hw0_i, scale0, scale1, mask0, mask1)
     out['conf_matrix'] = conf
     return out
 

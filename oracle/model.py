@@ -28,16 +28,36 @@ POSE_STD = np.array([1.94014405, 0.36770130, 1.88317520, 0.51837117, 0.12717603,
                      0.12717603, 0.0188729, 0.09709263], np.float32)          # loftr_loss.py:8
 
 
-def _t(a):
-    return torch.from_numpy(np.ascontiguousarray(a))
+def _t(a, dtype=None):
+    """numpy -> torch; dtype (a numpy float type) casts on the way (None: the array's own type)."""
+    a = np.ascontiguousarray(a)
+    return torch.from_numpy(a if dtype is None else a.astype(dtype, copy=False))
 
 
 class Weights:
-    def __init__(self, sd):
+    """dtype=None: parameters in their stored type (fp32).  dtype=np.float64: every parameter handed out as float64, so that the
+    torch-CPU functional ops of this module run in float64 on the same fp32 parameter values (`as64()` gives such a view)."""
+
+    def __init__(self, sd, dtype=None):
         self.sd = {k: (v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)) for k, v in sd.items()}
+        self.dtype = dtype
+        self._cache = {}
 
     def t(self, name):
-        return _t(self.sd[name])
+        if self.dtype is None:
+            return _t(self.sd[name])
+        a = self.sd[name]
+        if not np.issubdtype(a.dtype, np.floating):
+            return _t(a)
+        if name not in self._cache:
+            self._cache[name] = _t(a, self.dtype)
+        return self._cache[name]
+
+    def as_dtype(self, dtype):
+        """The same parameters handed out as `dtype` (np.float32 -> the stored values unchanged)."""
+        if dtype == np.float32 or dtype is None:
+            return self if self.dtype is None else Weights(self.sd)
+        return self if self.dtype == dtype else Weights(self.sd, dtype)
 
     def has(self, name):
         return name in self.sd
@@ -62,7 +82,7 @@ def _block(w, p, x, stride):
 def backbone(w, img):
     """resnet_fpn.py:101-119.  img (N,1,H,W) -> feats_c (N,256,H/8,W/8), feats_f (N,128,H/2,W/2)."""
     p = 'backbone.'
-    x0 = F.relu(_bn(w, p + 'bn1', F.conv2d(_t(img), w.t(p + 'conv1.weight'), stride=2, padding=3)))
+    x0 = F.relu(_bn(w, p + 'bn1', F.conv2d(_t(img, w.dtype), w.t(p + 'conv1.weight'), stride=2, padding=3)))
     x1 = _block(w, p + 'layer1.1', _block(w, p + 'layer1.0', x0, 1), 1)
     x2 = _block(w, p + 'layer2.1', _block(w, p + 'layer2.0', x1, 2), 1)
     x3 = _block(w, p + 'layer3.1', _block(w, p + 'layer3.0', x2, 2), 1)
@@ -101,12 +121,14 @@ def position_encoding(d_model, h, w, temp_bug_fix=True):
 # ---------------------------------------------------------------------------------------------------------
 # LoFTR encoder layers (transformer.py:44-67, :90-112)
 # ---------------------------------------------------------------------------------------------------------
-def encoder_layer(w, p, x, source, nhead):
-    xt, st = _t(x), _t(source)
+def encoder_layer(w, p, x, source, nhead, x_mask=None, source_mask=None):
+    """transformer.py:44-67.  x_mask (N, L) / source_mask (N, S): bool, into LinearAttention as q_mask / kv_mask (:58)."""
+    dt = np.float32 if w.dtype is None else w.dtype
+    xt, st = _t(x, w.dtype), _t(source, w.dtype)
     q = F.linear(xt, w.t(p + '.q_proj.weight')).numpy()
     k = F.linear(st, w.t(p + '.k_proj.weight')).numpy()
     v = F.linear(st, w.t(p + '.v_proj.weight')).numpy()
-    msg = oattn.linear_attention(q, k, v, nhead)                                     # linear_attention.py
+    msg = oattn.linear_attention(q, k, v, nhead, q_mask=x_mask, kv_mask=source_mask, dtype=dt)   # linear_attention.py
     C = x.shape[-1]
     msg = F.linear(_t(msg), w.t(p + '.merge.weight'))
     msg = F.layer_norm(msg, (C,), w.t(p + '.norm1.weight'), w.t(p + '.norm1.bias'))
@@ -115,59 +137,80 @@ def encoder_layer(w, p, x, source, nhead):
     return (xt + msg).numpy()
 
 
-def feature_transformer(w, p, feat0, feat1, layer_names, nhead):
+def feature_transformer(w, p, feat0, feat1, layer_names, nhead, mask0=None, mask1=None):
+    """transformer.py:90-112; the masks in the reference's order (:101-108)."""
     for i, name in enumerate(layer_names):
         lp = f'{p}.layers.{i}'
         if name == 'self':
-            feat0 = encoder_layer(w, lp, feat0, feat0, nhead)
-            feat1 = encoder_layer(w, lp, feat1, feat1, nhead)
+            feat0 = encoder_layer(w, lp, feat0, feat0, nhead, mask0, mask0)          # :101-102
+            feat1 = encoder_layer(w, lp, feat1, feat1, nhead, mask1, mask1)
         else:
-            feat0 = encoder_layer(w, lp, feat0, feat1, nhead)
-            feat1 = encoder_layer(w, lp, feat1, feat0, nhead)                        # updated feat0 (:107-108)
+            feat0 = encoder_layer(w, lp, feat0, feat1, nhead, mask0, mask1)          # :104-105
+            feat1 = encoder_layer(w, lp, feat1, feat0, nhead, mask1, mask0)          # updated feat0 (:107-108)
     return feat0, feat1
 
 
 # ---------------------------------------------------------------------------------------------------------
 # matcher forward (loftr.py:56-135)
 # ---------------------------------------------------------------------------------------------------------
-def matcher_forward(w, cfg, image0, image1, from_featmaps=None):
-    """Returns the data dict (numpy) the reference's LoFTR.forward would have produced (eval path)."""
+def matcher_forward(w, cfg, image0, image1, from_featmaps=None, mask0=None, mask1=None, scale0=None, scale1=None,
+                    dtype=np.float32):
+    """Returns the data dict (numpy) the reference's LoFTR.forward would have produced (eval path).
+
+    image0 / image1 of different sizes: two backbone runs (loftr.py:75-76), hw0_* / hw1_* kept apart.  mask0 / mask1 (N, h_c, w_c)
+    bool: the padded coarse masks of loftr.py:62-63, flattened into the coarse transformer and the coarse matcher (:103-111).
+    scale0 / scale1 (N, 2): coarse_matching.py:247-254, fine_matching.py:70-71.  dtype=np.float64: the whole path in float64 on
+    the same fp32 images and parameters (a high-precision reference, not a second fp32 run); the default reproduces the reference's
+    fp32 arithmetic and, with the other defaults, the results of earlier versions of this function bit for bit."""
     data = {}
+    w = w.as_dtype(dtype)
     if from_featmaps is None:
         N = image0.shape[0]
-        fc, ff = backbone(w, np.concatenate([image0, image1], 0))
-        fc0, fc1, ff0, ff1 = fc[:N], fc[N:], ff[:N], ff[N:]
-        hw_i = image0.shape[2:]
+        if image0.shape[2:] == image1.shape[2:]:                                      # loftr.py:72-74
+            fc, ff = backbone(w, np.concatenate([image0, image1], 0))
+            fc0, fc1, ff0, ff1 = fc[:N], fc[N:], ff[:N], ff[N:]
+        else:                                                                         # :75-76
+            (fc0, ff0), (fc1, ff1) = backbone(w, image0), backbone(w, image1)
+        hw0_i, hw1_i = image0.shape[2:], image1.shape[2:]
     else:
-        fc0, fc1, ff0, ff1, hw_i = from_featmaps
+        fc0, fc1, ff0, ff1, hw0_i = from_featmaps
+        hw1_i = hw0_i
         N = fc0.shape[0]
-    hw_c, hw_f = fc0.shape[2:], ff0.shape[2:]
+    hw0_c, hw0_f, hw1_c, hw1_f = fc0.shape[2:], ff0.shape[2:], fc1.shape[2:], ff1.shape[2:]
     C = fc0.shape[1]
-    pe = position_encoding(C, hw_c[0], hw_c[1], cfg['coarse']['temp_bug_fix'])
-    f0 = (fc0 + pe[None]).reshape(N, C, -1).transpose(0, 2, 1).copy()
-    f1 = (fc1 + pe[None]).reshape(N, C, -1).transpose(0, 2, 1).copy()
-    f0, f1 = feature_transformer(w, 'loftr_coarse', f0, f1, cfg['coarse']['layer_names'], cfg['coarse']['nhead'])
-    cm = ocoarse.coarse_matching(f0, f1, cfg['match_coarse'], hw_c, hw_c, hw_i)
+    tbf = cfg['coarse']['temp_bug_fix']
+    tok = lambda fc, hw: (fc + position_encoding(C, hw[0], hw[1], tbf)[None]).reshape(N, C, -1).transpose(0, 2, 1).copy()
+    f0, f1 = tok(fc0, hw0_c), tok(fc1, hw1_c)                                         # :100-101
+    m0 = m1 = None
+    if mask0 is not None:                                                             # :103-105
+        m0, m1 = np.asarray(mask0, bool).reshape(N, -1), np.asarray(mask1, bool).reshape(N, -1)
+    f0, f1 = feature_transformer(w, 'loftr_coarse', f0, f1, cfg['coarse']['layer_names'], cfg['coarse']['nhead'], m0, m1)
+    cm = ocoarse.coarse_matching(f0, f1, cfg['match_coarse'], hw0_c, hw1_c, hw0_i, m0, m1, scale0, scale1, dtype,
+                                 mask0=mask0, mask1=mask1, keep_input_precision=True)
     data.update(cm)
     b, i, j = cm['b_ids'], cm['i_ids'], cm['j_ids']
     W = cfg['fine_window_size']
-    stride = hw_f[0] // hw_c[0]
+    stride = hw0_f[0] // hw0_c[0]                                                     # fine_preprocess.py:31
     M = len(b)
     if M:
-        w0 = ofine.unfold_windows(ff0, b, i, hw_c[1], W, stride)                     # fine_preprocess.py:40-47
-        w1 = ofine.unfold_windows(ff1, b, j, hw_c[1], W, stride)
+        w0 = ofine.unfold_windows(ff0, b, i, hw0_c[1], W, stride)                    # fine_preprocess.py:40-47
+        w1 = ofine.unfold_windows(ff1, b, j, hw1_c[1], W, stride)
         cwin = F.linear(_t(np.concatenate([f0[b, i], f1[b, j]], 0)), w.t('fine_preprocess.down_proj.weight'),
                         w.t('fine_preprocess.down_proj.bias'))                        # :50-52
         both = torch.cat([_t(np.concatenate([w0, w1], 0)), cwin.unsqueeze(1).expand(-1, W * W, -1)], -1)
         both = F.linear(both, w.t('fine_preprocess.merge_feat.weight'), w.t('fine_preprocess.merge_feat.bias'))
         w0, w1 = both[:M].numpy(), both[M:].numpy()
         w0, w1 = feature_transformer(w, 'loftr_fine', w0, w1, cfg['fine']['layer_names'], cfg['fine']['nhead'])
-        scale = hw_i[0] / hw_f[0]
-        expec, mk1 = ofine.fine_matching(w0, w1, cm['mkpts1_c'], (W // 2) * scale)
+        scale = hw0_i[0] / hw0_f[0]
+        win_scale = (W // 2) * scale
+        if scale0 is not None:                                                        # fine_matching.py:70 (keyed on scale0, reads scale1)
+            win_scale = (W // 2) * (scale * np.asarray(scale1)[b])
+        expec, mk1 = ofine.fine_matching(w0, w1, cm['mkpts1_c'], win_scale, dtype=dtype)
         data.update({'expec_f': expec, 'mkpts0_f': cm['mkpts0_c'], 'mkpts1_f': mk1})
     else:
         data.update({'expec_f': np.zeros((0, 3), np.float32), 'mkpts0_f': cm['mkpts0_c'], 'mkpts1_f': cm['mkpts1_c']})
-    data.update({'featmap0': f0, 'featmap1': f1, 'hw0_c': hw_c, 'hw0_f': hw_f, 'hw0_i': hw_i, 'bs': N})
+    data.update({'featmap0': f0, 'featmap1': f1, 'hw0_c': hw0_c, 'hw0_f': hw0_f, 'hw0_i': hw0_i, 'bs': N,
+                 'hw1_c': hw1_c, 'hw1_f': hw1_f, 'hw1_i': hw1_i, 'featmap_f0': ff0, 'featmap_f1': ff1})
     return data
 
 

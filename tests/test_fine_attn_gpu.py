@@ -53,17 +53,73 @@ def test_fine_expect():
     np.testing.assert_allclose(expec.cpu().numpy(), e32, atol=1e-4, rtol=0)
 
 
-@pytest.mark.parametrize('N,L,S,C', [(2, 4800, 4800, 256), (3, 100, 333, 256), (700, 25, 25, 128)])
-def test_linear_attention(N, L, S, C):
+def _k5_masks(kind, N, L, S, hw=None):
+    """uint8 (N, L) / (N, S) masks of test_linear_attention.  'rect': rectangular padding masks on the hw grid (what a batch of
+    images padded to one canvas has), different per image; 'random'; 'q' / 'kv': one side only; 'kv_empty': image 0's kv-mask is
+    all false (nothing to attend to: the message is zero, not NaN)."""
+    rng = np.random.default_rng(7)
+    rand = lambda n: (rng.random((N, n)) < 0.7).astype(np.uint8)
+    if kind is None:
+        return None, None
+    if kind == 'rect':
+        h, w = hw
+        assert h * w == L == S
+        qm, km = np.zeros((N, h, w), np.uint8), np.zeros((N, h, w), np.uint8)
+        for n in range(N):
+            qm[n, :h - 7 * n - 3, :w - 11 * (1 - n % 2)] = 1
+            km[n, :h - 5 * (1 - n % 2), :w - 13 * n - 2] = 1
+        return qm.reshape(N, L), km.reshape(N, S)
+    if kind == 'random':
+        return rand(L), rand(S)
+    if kind == 'q':
+        return rand(L), None
+    if kind == 'kv':
+        return None, rand(S)
+    if kind == 'kv_empty':
+        km = rand(S)
+        km[0] = 0
+        return rand(L), km
+    raise ValueError(kind)
+
+
+_K5_CASES = [(2, 4800, 4800, 256, None), (3, 100, 333, 256, None), (700, 25, 25, 128, None),
+             (2, 4800, 4800, 256, 'rect'), (3, 100, 333, 256, 'random'), (3, 100, 333, 256, 'q'),
+             (3, 100, 333, 256, 'kv'), (3, 100, 333, 256, 'kv_empty'), (2, 48, 192, 256, 'random')]
+
+
+@pytest.mark.parametrize('N,L,S,C,masks', _K5_CASES,        # (the unmasked cases keep the ids they had before the masks came)
+                         ids=['-'.join(str(x) for x in c[:4]) + ('' if c[4] is None else '-' + c[4]) for c in _K5_CASES])
+def test_linear_attention(N, L, S, C, masks):
+    """K5 against the float64 definition; with q_mask / kv_mask (linear_attention.py:38-42) as uint8, the type the op takes."""
     from far_amd import ops
     from oracle import attention as oa
     rng = np.random.default_rng(2)
     q = rng.standard_normal((N, L, C)).astype(np.float32)
     k = rng.standard_normal((N, S, C)).astype(np.float32)
     v = rng.standard_normal((N, S, C)).astype(np.float32)
-    got = ops.linear_attention(*(torch.from_numpy(a).cuda() for a in (q, k, v)), 8).cpu().numpy()
-    ref = oa.linear_attention(q, k, v, 8, dtype=np.float64)
+    qm, km = _k5_masks(masks, N, L, S, hw=(60, 80))
+    cu = lambda a: None if a is None else torch.from_numpy(a).cuda()
+    got = ops.linear_attention(cu(q), cu(k), cu(v), 8, cu(qm), cu(km)).cpu().numpy()
+    ref = oa.linear_attention(q, k, v, 8, q_mask=qm, kv_mask=km, dtype=np.float64)
+    assert np.isfinite(got).all()
     np.testing.assert_allclose(got, ref, atol=1e-5 * np.abs(ref).max(), rtol=1e-4)
+    if masks is not None:
+        plain = oa.linear_attention(q, k, v, 8, dtype=np.float64)
+        assert np.abs(ref - plain).max() > 1e-2 * np.abs(ref).max()          # the masks matter on this input
+    if qm is not None:
+        assert (got[qm == 0] == 0).all()                                     # a masked query row is exactly zero
+    if masks == 'kv_empty':
+        assert (got[0] == 0).all()
+
+
+def test_linear_attention_refuses_a_bool_mask():
+    """The op reads its masks as bytes: any other type is refused before a launch, not reinterpreted."""
+    from far_amd import _lib, ops
+    q = torch.randn(2, 70, 256, device='cuda')
+    bad = torch.ones(2, 70, dtype=torch.bool, device='cuda')
+    for kw in ({'q_mask': bad}, {'kv_mask': bad}, {'q_mask': bad.float()}):
+        with pytest.raises(_lib.FarHipError, match='dtype'):
+            ops.linear_attention(q, q, q, 8, **kw)
 
 
 @pytest.mark.parametrize('N,Hf,Wf,M,Cout', [(4, 48, 64, 300, 128), (2, 30, 44, 777, 128), (3, 24, 32, 1, 128), (2, 48, 64, 500, 256)])

@@ -237,6 +237,47 @@ def test_g7_full_matcher_forward():
     np.testing.assert_allclose(data['expec_f'][a], g['expec_f'][b], atol=5e-3, rtol=0)
 
 
+# ------------------------------------------------------------------------------------------------ G20
+@pytest.mark.timeout(900)
+@pytest.mark.parametrize('case', ['unequal', 'short_side', 'masked', 'masked_unequal', 'masked_all_true'])
+def test_g20_matcher_forward_offdefault(case):
+    """The extended oracle (unequal sizes, padded masks, scales) in fp32 against the reference's own run (G20), at the bars
+    test_g7_full_matcher_forward uses: this pins the extension to the reference before a GPU test leans on it."""
+    from oracle import model as om
+    from tests.util import g20_common, g20_input_conditions, offdefault_inputs
+    g = load('g20_matcher_offdefault')
+    g20_input_conditions(g, case)
+    man = json.load(open(os.path.join(G, 'g8_state_dict_manifest.json')))
+    w = om.Weights(synth.synthetic_state_dict({k: tuple(v) for k, v in man.items()}))
+    inp = offdefault_inputs(case)
+    data = om.matcher_forward(w, far_eval_config(), inp['image0'], inp['image1'], mask0=inp.get('mask0'), mask1=inp.get('mask1'),
+                              scale0=inp.get('scale0'), scale1=inp.get('scale1'))
+    assert tuple(data['hw0_c']) == tuple(g[f'{case}__hw0_c']) and tuple(data['hw1_c']) == tuple(g[f'{case}__hw1_c'])
+    st = int(g[f'{case}__token_stride'])
+    for k in ('featmap0', 'featmap1'):
+        np.testing.assert_allclose(data[k][:, ::st], g[f'{case}__{k}'], atol=2e-3, rtol=1e-3)
+    a, b = g20_common(g, case, (data['b_ids'], data['i_ids'], data['j_ids']), 1e-3, 0.98)
+    for k in ('mkpts0_c', 'mkpts1_c'):
+        np.testing.assert_allclose(data[k][a], g[f'{case}__{k}'][b], rtol=1e-6, atol=0)
+    np.testing.assert_allclose(data['mconf'][a], g[f'{case}__mconf'][b], atol=5e-3, rtol=0)
+    np.testing.assert_allclose(data['mkpts1_f'][a], g[f'{case}__mkpts1_f'][b], atol=2e-2, rtol=0)
+    np.testing.assert_allclose(data['expec_f'][a], g[f'{case}__expec_f'][b], atol=5e-3, rtol=0)
+
+
+def test_oracle_padding_border_equals_plain_border_on_full_extents():
+    """mask_border_with_padding with full extents is mask_border (coarse_matching.py:8-43)."""
+    from oracle import coarse as oc
+    rng = np.random.default_rng(3)
+    a = rng.random((2, 6, 8, 5, 7)) > 0.3
+    b = a.copy()
+    oc.mask_border(a, 2, False)
+    oc.mask_border_with_padding(b, 2, False, np.ones((2, 6, 8), bool), np.ones((2, 5, 7), bool))
+    np.testing.assert_array_equal(a, b)
+    m0 = np.zeros((2, 6, 8), bool); m0[0, :5, :7] = True; m0[1, :6, :4] = True
+    m1 = np.zeros((2, 5, 7), bool); m1[0, :3, :7] = True; m1[1, :5, :6] = True
+    np.testing.assert_array_equal(oc.valid_extents(m0, m1), [[5, 7, 3, 7], [6, 4, 5, 6]])
+
+
 # ------------------------------------------------------------------------------------------------ G11
 @pytest.mark.timeout(900)
 def test_g11_matcher_forward_544x720():

@@ -424,9 +424,8 @@ def test_training_step_on_gpu(model, monkeypatch):
         worst = max(worst, rel)
         print(f'[train grad] {k}: |g| {gr.norm().item():.6e} vs reference {g["grad_norms"][n]:.6e} (rel {rel:.2e})')
         s_ = gr.reshape(-1)[:: max(1, gr.numel() // 8)][:8].cpu().numpy()
-        if os.environ.get('FAR_MEASURE_ONLY') != '1':
-            np.testing.assert_allclose(gr.norm().item(), g['grad_norms'][n], rtol=5e-3, err_msg=k)
-            np.testing.assert_allclose(s_, g['grad_samples'][n], rtol=2e-2, atol=4e-3 * np.abs(g['grad_samples'][n]).max() + 1e-7, err_msg=k)
+        np.testing.assert_allclose(gr.norm().item(), g['grad_norms'][n], rtol=5e-3, err_msg=k)
+        np.testing.assert_allclose(s_, g['grad_samples'][n], rtol=2e-2, atol=4e-3 * np.abs(g['grad_samples'][n]).max() + 1e-7, err_msg=k)
     print(f'[train grad] worst relative deviation of a gradient norm: {worst:.2e}')
     n_grad = 0
     for k, p in m.named_parameters():

@@ -64,9 +64,7 @@ def deviation(name, got, ref, atol, rtol=0.0):
     d = float(np.abs(g.astype(np.float64) - r.astype(np.float64)).max()) if g.size else 0.0
     scale = float(np.abs(r).max()) if r.size else 1.0
     print(f'[deviation] {name}: max|d| = {d:.3e}  (max|ref| = {scale:.3e}, rel = {d / max(scale, 1e-30):.3e}; bar atol {atol:g} rtol {rtol:g})')
-    import os
-    if os.environ.get('FAR_MEASURE_ONLY') != '1':          # measurement runs print every deviation without stopping
-        np.testing.assert_allclose(g, r, atol=atol, rtol=rtol, err_msg=name)
+    np.testing.assert_allclose(g, r, atol=atol, rtol=rtol, err_msg=name)
     return d
 
 
@@ -295,6 +293,123 @@ def masked_coarse_inputs(seed=91, N=2, h=24, w=32, C=256):
     order = np.lexsort((np.array(ii), np.array(bb)))
     return {'f0': f0, 'f1': f1, 'mask0': m0, 'mask1': m1, 'spv_b_ids': np.array(bb, np.int64)[order],
             'spv_i_ids': np.array(ii, np.int64)[order], 'spv_j_ids': np.array(jj, np.int64)[order], 'h': h, 'w': w}
+
+
+# ---- golden G20 (the matcher off its default launch sequence): inputs shared by tools/make_goldens.py:g20 and the tests
+# Per case: the seed and size of far_amd.synth.synth_image_pair, its band disparities, the top-left crops of the two images,
+# and for the padded cases each pair's valid extents (h0, w0, h1, w1) in coarse cells and the scale0 / scale1 rows (x, y).
+_EXT_MASKED = [(30, 34, 26, 40), (24, 40, 30, 36)]              # on the 30 x 40 grid; height != width in every extent
+_EXT_MASKED_UNEQUAL = [(24, 28, 16, 40), (20, 32, 20, 34)]      # on the 24 x 32 / 20 x 40 grids
+_SCALE0 = [[1.25, 1.5], [0.8, 1.1]]
+_SCALE1 = [[0.9, 1.35], [1.6, 0.75]]
+OFFDEFAULT = {
+    # two backbone runs, unstacked self layers, L != S in every cross launch, hw1_c[1] != hw0_c[1]
+    'unequal': dict(seed=31, hw=(192, 320), disparities=(8, 40, 72), crop0=(192, 256), crop1=(160, 320), min_matches=50),
+    # image 0 under 64 coarse tokens (6 x 8), image 1 above (12 x 16); disparity 0 in the band that holds image 0's 2 x 4 interior
+    'short_side': dict(seed=32, hw=(96, 128), disparities=(0, 8, 16), crop0=(48, 64), crop1=(96, 128), min_matches=8),
+    # one canvas, padded masks, scales
+    'masked': dict(seed=33, hw=(240, 320), disparities=(8, 40, 72), crop0=(240, 320), crop1=(240, 320), min_matches=50,
+                   extents=_EXT_MASKED, scale0=_SCALE0, scale1=_SCALE1),
+    # all of it together (a MegaDepth-style batch)
+    'masked_unequal': dict(seed=34, hw=(192, 320), disparities=(8, 40, 72), crop0=(192, 256), crop1=(160, 320), min_matches=50,
+                           extents=_EXT_MASKED_UNEQUAL, scale0=_SCALE0, scale1=_SCALE1),
+    # masks of ones on the unpadded images of 'masked': by definition the same function as no masks at all
+    'masked_all_true': dict(seed=33, hw=(240, 320), disparities=(8, 40, 72), crop0=(240, 320), crop1=(240, 320), min_matches=50,
+                            extents=[(30, 40, 30, 40)] * 2, scale0=_SCALE0, scale1=_SCALE1),
+}
+OFFDEFAULT_MASKED = ('masked', 'masked_unequal', 'masked_all_true')
+
+
+def offdefault_inputs(case, N=2, canvas=None):
+    """One G20 case as numpy: image0 / image1 (N, 1, H, W) float32, and for the padded cases mask0 / mask1 (N, h, w) bool on the
+    coarse grids, scale0 / scale1 (N, 2) float32 and `extents` (N, 4) int (h0, w0, h1, w1).  The two images of
+    far_amd.synth.synth_image_pair are cropped from the top-left corner (the band disparities still give true matches); the pixels
+    beyond a valid extent are zero.  N > 2 repeats the extents / scales of the two pairs on fresh images; canvas=(H, W) enlarges an
+    equal-canvas case (extents scaled with it) -- the bench-grid determinism test uses both."""
+    from far_amd import synth
+    c = OFFDEFAULT[case]
+    hw, crop0, crop1 = c['hw'], c['crop0'], c['crop1']
+    ext = c.get('extents')
+    if canvas is not None:
+        assert crop0 == crop1 == hw and canvas[0] % hw[0] == 0 and canvas[1] % hw[1] == 0 and canvas[0] // hw[0] == canvas[1] // hw[1]
+        k = canvas[0] // hw[0]
+        hw = crop0 = crop1 = tuple(canvas)
+        ext = [tuple(k * e for e in row) for row in ext] if ext is not None else None
+    im0, im1 = synth.synth_image_pair(N, seed=c['seed'], hw=hw, disparities=c['disparities'])
+    out = {'image0': np.ascontiguousarray(im0[:, :, :crop0[0], :crop0[1]]),
+           'image1': np.ascontiguousarray(im1[:, :, :crop1[0], :crop1[1]])}
+    if ext is not None:
+        ext = np.array([ext[n % len(ext)] for n in range(N)], np.int64)
+        m0 = np.zeros((N, crop0[0] // 8, crop0[1] // 8), bool)
+        m1 = np.zeros((N, crop1[0] // 8, crop1[1] // 8), bool)
+        for n, (h0, w0, h1, w1) in enumerate(ext):
+            m0[n, :h0, :w0] = True
+            m1[n, :h1, :w1] = True
+            out['image0'][n, :, 8 * h0:] = 0
+            out['image0'][n, :, :, 8 * w0:] = 0
+            out['image1'][n, :, 8 * h1:] = 0
+            out['image1'][n, :, :, 8 * w1:] = 0
+        out.update(mask0=m0, mask1=m1, extents=ext,
+                   scale0=np.array([c['scale0'][n % 2] for n in range(N)], np.float32),
+                   scale1=np.array([c['scale1'][n % 2] for n in range(N)], np.float32))
+    return out
+
+
+def offdefault_data(inp, device='cpu', masks=True):
+    """The data dict LoFTR.forward takes (loftr.py:59-64; coarse_matching.py:247-248 for the scales) from offdefault_inputs."""
+    import torch
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+    data = {'image0': t(inp['image0']), 'image1': t(inp['image1'])}
+    if 'mask0' in inp and masks:
+        data.update(mask0=t(inp['mask0']), mask1=t(inp['mask1']))
+    if 'scale0' in inp:
+        data.update(scale0=t(inp['scale0']), scale1=t(inp['scale1']))
+    return data
+
+
+def margin_rows(g, case, thr=0.2, margin=1e-4):
+    """G7's margin protocol on a G20 case: the rows (b, i) of the reference's conf_matrix whose top-2 gap, whose best column's
+    top-2 gap and whose distance of the row maximum to the threshold all exceed `margin` -> bool (N, L)."""
+    rowmax, rowgap, colgap, rowarg = (g[f'{case}__{k}'] for k in ('rowmax', 'rowgap', 'colgap', 'rowarg'))
+    return (np.abs(rowmax - thr) > margin) & (rowgap > margin) & (np.take_along_axis(colgap, rowarg, 1) > margin)
+
+
+def g20_input_conditions(g, case):
+    """The conditions the G20 inputs were chosen under, re-checked from the fixture (the generator asserts them against the
+    reference's own output): enough matches, the padding-aware far border removes matches, >= 90 % of the matches on margin rows."""
+    M = len(g[f'{case}__b_ids'])
+    removed = int(g[f'{case}__removed_by_padding_border'])
+    frac = float(margin_rows(g, case)[g[f'{case}__b_ids'], g[f'{case}__i_ids']].mean())
+    print(f'[g20 {case}] reference matches {M}, removed by the padding-aware border {removed}, on margin rows {frac:.3f}')
+    assert M >= OFFDEFAULT[case]['min_matches']
+    if case in ('masked', 'masked_unequal'):
+        assert removed > 0
+    assert frac >= 0.9
+
+
+def ids_protocol(what, got_ids, ref_ids, safe, min_common):
+    """G7's id protocol on a batch.  got_ids / ref_ids: (b_ids, i_ids, j_ids); safe: bool (N, L), the rows with margin.  On those
+    rows the match decision and j are identical; more than `min_common` of the reference's matches are common.
+    -> (indices into the tested arrays, indices into the reference's) of the common matches."""
+    got = {(b, i): j for b, i, j in zip(*(np.asarray(a).tolist() for a in got_ids))}
+    ref = {(b, i): j for b, i, j in zip(*(np.asarray(a).tolist() for a in ref_ids))}
+    print(f'[{what}] rows with margin: {int(safe.sum())} of {safe.size}; matches got {len(got)} / reference {len(ref)}')
+    for b, i in zip(*np.nonzero(safe)):
+        key = (int(b), int(i))
+        assert (key in got) == (key in ref), (what, key)
+        if key in got:
+            assert got[key] == ref[key], (what, key)
+    common = [k for k in ref if k in got]
+    assert len(common) > min_common * len(ref), (what, len(common), len(ref))
+    gi = {k: n for n, k in enumerate(got)}
+    ri = {k: n for n, k in enumerate(ref)}
+    return np.array([gi[k] for k in common], np.int64), np.array([ri[k] for k in common], np.int64)
+
+
+def g20_common(g, case, got_ids, margin, min_common):
+    """ids_protocol against a G20 case, with the margins of the reference's own conf_matrix."""
+    return ids_protocol(f'g20 {case}', got_ids, tuple(g[f'{case}__{k}'] for k in ('b_ids', 'i_ids', 'j_ids')),
+                        margin_rows(g, case, margin=margin), min_common)
 
 
 # ---- golden G19 (the 8-Point-ViT shape of K2): the seeded weights / input both tools/make_golden_vit.py and the tests replay

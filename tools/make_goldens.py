@@ -2,7 +2,9 @@
 
 Container-only: needs /root/reference and tools/ref_shim.py.  The fixtures are data (seeds, small inputs,
 expected outputs); no reference source is copied.  Weights come from far_amd.synth (seeded), inputs from
-seeds recorded in each file.  Run:  python tools/make_goldens.py
+seeds recorded in each file.  Run:  python tools/make_goldens.py  (all of g1 ... g18 and g20; `python tools/make_goldens.py g20`
+for one; g19 comes from tools/make_golden_vit.py).  g20 = LoFTR.forward off the default launch sequence of far_amd (unequal image
+sizes, padded masks, scales), with the fp32 run's deviation from the float64 oracle stored next to it.
 """
 import importlib.util
 import json
@@ -643,6 +645,86 @@ def g18_masked_training_coarse():
     save('g18_masked_training_coarse', **out)
 
 
+def g20_matcher_offdefault(m):
+    """LoFTR.forward (loftr.py:194-205, eval) off the default launch sequence of far_amd: images of unequal size (:75-76), padded
+    coarse masks (:103-111; coarse_matching.py:28-43, :110-117, :177-181), scale0 / scale1 (coarse_matching.py:247-254,
+    fine_matching.py:70-71), one image under 64 coarse tokens.  Inputs: tests/util.py:offdefault_inputs (seeds and sizes stored,
+    not images).  Also stored per case: dev32_* = the deviation of this fp32 run from oracle.model.matcher_forward in float64 on
+    the same inputs -- what fp32 arithmetic itself loses.
+
+    The reference's forward_feature_extraction reads `feats_c` in its unequal-size branch without ever assigning it (loftr.py:75-89:
+    UnboundLocalError); for those cases the generator writes the keys of :67-89 itself from the reference's backbone (feats_c = None,
+    which nothing reads with predict_translation_scale off) and calls the reference's forward_correspondence_prediction."""
+    from oracle import coarse as oc
+    from oracle import model as om
+    from tests.util import OFFDEFAULT, OFFDEFAULT_MASKED, margin_rows, offdefault_data, offdefault_inputs
+    cfg = ref_shim.far_eval_config()
+    mc = cfg['match_coarse']
+    w = om.Weights({k: v for k, v in m.state_dict().items()})
+    out = {'note': 'coarse tokens subsampled: every 47th row per image (short_side: every 5th); fine maps [:, ::16, ::7, ::9]; '
+                   'coarse backbone maps [:, ::16, ::3, ::5]; unequal-size cases: see tools/make_goldens.py:g20 on loftr.py:75-89'}
+    for case, c in OFFDEFAULT.items():
+        inp = offdefault_inputs(case)
+        data = offdefault_data(inp)
+        n = inp['image0'].shape[0]
+        with torch.no_grad():
+            if inp['image0'].shape == inp['image1'].shape:
+                m(data)
+                c0, c1 = data['feats_c'].split(n)
+            else:
+                try:
+                    m(dict(data))
+                    raise AssertionError('the reference ran the unequal-size branch: drop the workaround')
+                except UnboundLocalError:
+                    pass
+                (c0, f0), (c1, f1) = m.backbone(data['image0']), m.backbone(data['image1'])
+                data.update(bs=n, hw0_i=data['image0'].shape[2:], hw1_i=data['image1'].shape[2:], hw0_c=c0.shape[2:],
+                            hw1_c=c1.shape[2:], hw0_f=f0.shape[2:], hw1_f=f1.shape[2:], featmap0=c0, featmap1=c1, featmap_f0=f0,
+                            featmap_f1=f1, feats_c=None)
+                m.forward_correspondence_prediction(data)
+        conf = data['conf_matrix']
+        rs, cs = torch.sort(conf, dim=2)[0], torch.sort(conf, dim=1)[0]
+        st = 5 if case == 'short_side' else 47
+        r = {'seed': c['seed'], 'hw0_i': tuple(data['hw0_i']), 'hw1_i': tuple(data['hw1_i']),
+             'hw0_c': tuple(data['hw0_c']), 'hw1_c': tuple(data['hw1_c']), 'token_stride': st,
+             'rowmax': rs[..., -1].numpy(), 'rowgap': (rs[..., -1] - rs[..., -2]).numpy(), 'rowarg': conf.argmax(2).numpy(),
+             'colgap': (cs[:, -1] - cs[:, -2]).numpy(),
+             'featmap0': data['featmap0'][:, ::st].numpy(), 'featmap1': data['featmap1'][:, ::st].numpy(),
+             'featc0_sample': c0[:, ::16, ::3, ::5].numpy(), 'featc1_sample': c1[:, ::16, ::3, ::5].numpy(),
+             'featmap_f0_sample': data['featmap_f0'][:, ::16, ::7, ::9].numpy(),
+             'featmap_f1_sample': data['featmap_f1'][:, ::16, ::7, ::9].numpy()}
+        for k in ('b_ids', 'i_ids', 'j_ids', 'mconf', 'mkpts0_c', 'mkpts1_c', 'mkpts0_f', 'mkpts1_f', 'expec_f'):
+            r[k] = data[k].numpy()
+        M = len(r['b_ids'])
+        # conditions on the inputs (ISSUE part 1), against the reference's own output
+        assert M >= c['min_matches'], (case, M)
+        plain = oc.get_coarse_match(conf.numpy(), mc['thr'], mc['border_rm'], data['hw0_c'], data['hw1_c'], data['hw0_i'])
+        removed = len(plain['b_ids']) - M
+        r['removed_by_padding_border'] = removed
+        if case in OFFDEFAULT_MASKED:
+            assert removed == 0 if case == 'masked_all_true' else removed > 0, (case, removed)
+        safe = margin_rows({f'{case}__{k}': v for k, v in r.items()}, case, mc['thr'])
+        frac = float(safe[r['b_ids'], r['i_ids']].mean())
+        assert frac >= 0.9, (case, frac)
+        # what fp32 itself loses: this run against the float64 oracle on the same inputs
+        o = om.matcher_forward(w, cfg, inp['image0'], inp['image1'], mask0=inp.get('mask0'), mask1=inp.get('mask1'),
+                               scale0=inp.get('scale0'), scale1=inp.get('scale1'), dtype=np.float64)
+        dmax = lambda a, b: float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max())
+        r['dev32_tokens'] = max(dmax(data['featmap0'].numpy(), o['featmap0']), dmax(data['featmap1'].numpy(), o['featmap1']))
+        oi = {(b, i): k for k, (b, i) in enumerate(zip(o['b_ids'].tolist(), o['i_ids'].tolist()))}
+        both = [(k, oi[bi]) for k, bi in enumerate(zip(r['b_ids'].tolist(), r['i_ids'].tolist())) if bi in oi]
+        a, b = np.array([x for x, _ in both]), np.array([y for _, y in both])
+        assert (r['j_ids'][a] == o['j_ids'][b]).mean() > 0.99 and len(a) > 0.99 * M
+        for k in ('mconf', 'mkpts1_f', 'expec_f'):
+            r['dev32_' + k] = dmax(r[k][a], o[k][b])
+        print(f'g20 {case}: matches {M} (float64 oracle {len(o["b_ids"])}, common {len(a)}), removed by the padding border {removed}, '
+              f'margin rows among matches {frac:.3f}, dev32 tokens {r["dev32_tokens"]:.2e} mconf {r["dev32_mconf"]:.2e} '
+              f'mkpts1_f {r["dev32_mkpts1_f"]:.2e} expec_f {r["dev32_expec_f"]:.2e}')
+        out.update({f'{case}__{k}': (v.astype(np.float32) if isinstance(v, np.ndarray) and v.dtype == np.float64 else v)
+                    for k, v in r.items()})
+    save('g20_matcher_offdefault', **out)
+
+
 def g8_manifest(m):
     man = {k: list(v.shape) for k, v in m.state_dict().items()}
     with open(os.path.join(OUT, 'g8_state_dict_manifest.json'), 'w') as f:
@@ -680,6 +762,9 @@ if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'g18':
         g18_masked_training_coarse()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'g20':
+        g20_matcher_offdefault(ref_model()[0])
+        sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == 'g17':
         g17_fivepoint()
         sys.exit(0)
@@ -693,8 +778,8 @@ if __name__ == '__main__':
     g3_encoder(model)
     g4_head(model)
     g7_full(model)
-    g10_training(model)
-    g11_matcher_544x720(model)
+    g10_training(model)             # a training-mode forward: it moves the BatchNorm running statistics of `model`
+    g11_matcher_544x720(ref_model()[0])      # ... so the fixtures behind it get a fresh model, as their one-fixture runs above do
     g12_ransac_loop()
     g13_mapfree_corr_volume_warp()
     g14_spvs_coarse()
@@ -702,3 +787,4 @@ if __name__ == '__main__':
     g16_eval_metrics()
     g17_fivepoint()
     g18_masked_training_coarse()
+    g20_matcher_offdefault(ref_model()[0])
