@@ -1,6 +1,7 @@
 """Default model configuration: the dict the reference hands to LoFTR(config=...), i.e.
 lower_config(cfg)['loftr'] (mp3d_loftr/src/lightning/lightning_loftr.py:40-50) for the FAR evaluation
-setting (mp3d_loftr/scripts/eval_matterport.sh:27-37, demo.py:58-99).  Plain data, same keys/values."""
+setting (mp3d_loftr/scripts/eval_matterport.sh:27-37, demo.py:58-99).  Plain data, same keys/values.
+'attention' of the 'coarse', 'fine' and 'regress' blocks: 'linear' (FAR) or 'full' (softmax attention, inference only), per block."""
 import copy
 
 FAR_EVAL_CONFIG = {

@@ -112,6 +112,8 @@ class LoFTR(nn.Module):
     # fp32-grade products -- is the ONLY parity configuration.  Every 16-bit stage below changes results (ids are no longer bit-exact,
     # the solver's pose error on the bench pairs grows: bench.py `other_modes` / `precision_stages` report it per stage); they exist
     # because BASELINE configs[1] names a 16-bit operand class, and are never what `value` is measured on.
+    # (The full softmax attention core of an attention = 'full' block, K22, has no 16-bit-operand variant: in such a block the stages
+    # below act on the layer's Linear launches only.)
     STAGES = ('trunk',          # backbone trunk (stem excluded): K9 on plain fp16 operands instead of K17 / K9 on split pairs
               'fpn',            # the FPN's fine branch (layer1 / layer2 outconvs): coarse features and match decisions unchanged
               'coarse_dense',   # d_model-256 layers (coarse transformer + the head's two): merge / MLP launches on plain fp16

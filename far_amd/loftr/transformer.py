@@ -5,7 +5,7 @@ checkpoints load unchanged:
   LoFTREncoderLayer :12-67, LocalFeatureTransformer :69-112, get_positional_encodings :183-248,
   CrossAttention :250-303, CrossBlock :305-348, LocalFeatureTransformerRegressor :350-499
 and of mp3d_loftr/src/loftr/loftr_module/vit_layers/mlp.py:8-28 (Mlp).
-The attention cores run in libfar_hip.so: K5 (linear attention) and K2 (bilinear dual-softmax, never
+The attention cores run in libfar_hip.so: K5 (linear attention), K22 (full softmax attention, inference) and K2 (bilinear dual-softmax, never
 materialising the (B, 4, 4800, 4800) score tensors), K6 (LayerNorm) and K9 / K15 (every Linear layer of the inference path).
 
 Batch semantics: the reference head is batch-size-1 only (its pairing reshape :339-341 and the gate
@@ -48,6 +48,28 @@ class LinearAttention(nn.Module):
         return out.view(N, L, H, D)
 
 
+class FullAttention(nn.Module):
+    """Module-shaped handle on K22 (reference: linear_attention.py:55-88), inference only.  No parameters: state dicts are those of
+    the linear form.  Masks follow the kernel's convention: a masked key is selected out, a padded query row is
+    exact zeros -- the reference's masked form returns NaN rows there."""
+
+    def __init__(self, use_dropout=False, attention_dropout=0.1, use_num_corres=False):
+        super().__init__()
+        self.use_dropout = use_dropout
+        self.attention_dropout = attention_dropout       # kept for the constructor's signature: dropout exists in training only
+        self.use_num_corres = use_num_corres
+
+    def forward(self, queries, keys, values, q_mask=None, kv_mask=None, loftr_preds=None):
+        N, L, H, D = queries.shape
+        S = keys.shape[1]
+        if ag.needs_grad(queries, keys, values) or (self.training and self.use_dropout):
+            raise NotImplementedError('FullAttention: training / gradients through the softmax attention core are not built '
+                                      '(inference only)')
+        out = ops.full_attention(queries.reshape(N, L, H * D).contiguous(), keys.reshape(N, S, H * D).contiguous(),
+                                 values.reshape(N, S, H * D).contiguous(), H, q_mask, kv_mask)
+        return out.view(N, L, H, D)
+
+
 class LoFTREncoderLayer(nn.Module):
     split_operands = True        # K9 operand precision of the Linear layers (False: plain fp16, LoFTR.set_precision)
     dense_split = True           # ... of the launches that are plain Linear layers at d_model 256 (merge, mlp[0], mlp[2]): False =
@@ -63,14 +85,15 @@ class LoFTREncoderLayer(nn.Module):
 
     def __init__(self, d_model, nhead, attention='linear', use_num_corres=False):
         super().__init__()
-        if attention != 'linear':
-            raise NotImplementedError("only attention='linear' (the FAR configuration) has a kernel")
+        if attention not in ('linear', 'full'):
+            raise NotImplementedError(f"attention={attention!r}: only 'linear' (the FAR configuration) and 'full' have kernels")
+        self.full = attention == 'full'          # softmax attention core (K22): inference only, no fused form (see forward)
         self.dim = d_model // nhead
         self.nhead = nhead
         self.q_proj = nn.Linear(d_model, d_model, bias=False)
         self.k_proj = nn.Linear(d_model, d_model, bias=False)
         self.v_proj = nn.Linear(d_model, d_model, bias=False)
-        self.attention = LinearAttention(use_num_corres=use_num_corres)
+        self.attention = FullAttention(use_num_corres=use_num_corres) if self.full else LinearAttention(use_num_corres=use_num_corres)
         self.merge = nn.Linear(d_model, d_model, bias=False)
         self.mlp = nn.Sequential(
             nn.Linear(d_model * 2, d_model * 2, bias=False),
@@ -82,6 +105,11 @@ class LoFTREncoderLayer(nn.Module):
 
     def forward(self, x, source, x_mask=None, source_mask=None, loftr_preds=None, out=None):
         bs = x.size(0)
+        if self.full and x.is_cuda and ag.needs_grad(x, source, self.norm1.weight):
+            raise NotImplementedError("LoFTREncoderLayer(attention='full'): training / gradients through the softmax attention core "
+                                      'are not built (inference only)')
+        if self.full and not x.is_cuda:
+            raise ops._lib.FarHipError("LoFTREncoderLayer(attention='full') needs tensors on the GPU (no CPU fallback exists)")
         if ag.needs_grad(x, source, self.norm1.weight) or not x.is_cuda:
             if (x.is_cuda and self.hip_training and self.layer_node and x_mask is None and source_mask is None and x.numel()
                     and source.numel() and self.dim in (16, 32) and x.shape[-1] % 4 == 0 and x.shape[-1] <= 512 and torch.is_grad_enabled()):
@@ -115,7 +143,9 @@ class LoFTREncoderLayer(nn.Module):
         heads = lambda t: t.view(bs, -1, self.nhead, self.dim)
         fuse = True     # measured: q | k | v (and k | v) in one launch pays at d_model 256 and, with 128-channel blocks, at 128
         source = source.contiguous()
-        if (self.fused_attn and x.shape[-1] == 128 and self.nhead == 8 and x.shape[1] <= 32 and source.shape[1] <= 32
+        # a 'full' layer takes none of the linear-attention fusions below (K14, the k | v state, the q apply): the q | k | v projection
+        # launch, K22, then the same merge + LN and MLP launches as the linear form
+        if (not self.full and self.fused_attn and x.shape[-1] == 128 and self.nhead == 8 and x.shape[1] <= 32 and source.shape[1] <= 32
                 and x_mask is None and source_mask is None):
             # d_model 128 on short sequences (the fine-level windows: bandwidth-bound): the whole layer in two launches --
             # K14 (q / k / v projections, linear attention, merge, norm1) and K13 (the MLP block, norm2, residual)
@@ -130,7 +160,7 @@ class LoFTREncoderLayer(nn.Module):
             h = ops.linear_f16s(x, lin('mlp0', self.mlp[0]), act='relu', x2=msg)
             return ops.linear_f16s(h, lin('mlp2', self.mlp[2]), ln=(self.norm2.weight, self.norm2.bias, self.norm2.eps),
                                    post_residual=x, out=out)
-        if (self.fused_kv and x.shape[-1] == 256 and self.nhead == 8 and source.shape[1] >= 64 and x_mask is None
+        if (not self.full and self.fused_kv and x.shape[-1] == 256 and self.nhead == 8 and source.shape[1] >= 64 and x_mask is None
                 and source_mask is None):
             # d_model 256 (the coarse level, the head's layers): the k | v projection ends in K'^T V (linear_attention.py:38-45)
             # instead of a store -- k and v (4 of the layer's 19 passes over a (rows, 256) tensor) never exist.  Partial sums are

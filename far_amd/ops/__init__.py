@@ -5,7 +5,7 @@ far_amd/ops.py, split):
     packs      weight images (PackedConv, PackedWino, the pack table, PackCache)
     conv       K9 / K17 / K10 convolutions, K19 BatchNorm, K8 upsample-add, K7 affine epilogues
     linear     K9 in Linear mode (plain, gather, k|v-state, q-apply)
-    attention  K5 linear attention, K6 LayerNorm
+    attention  K5 linear attention, K22 full attention, K6 LayerNorm
     coarse     K1
     fine       K3, K13, K14
     head       K2 + contraction, K4 front end, K11, K15, K12

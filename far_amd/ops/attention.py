@@ -1,4 +1,4 @@
-"""far_amd.ops.attention: K5 linear attention and K6 LayerNorm (forward, backward, training wrappers) (one family of the torch-tensor front ends for the C ABI in include/far_hip.h; far_amd/ops/__init__.py
+"""far_amd.ops.attention: K5 linear attention, K22 full attention and K6 LayerNorm (forward, backward, training wrappers) (one family of the torch-tensor front ends for the C ABI in include/far_hip.h; far_amd/ops/__init__.py
 re-exports everything under the flat far_amd.ops namespace the rest of the package uses)."""
 import ctypes
 import os
@@ -7,7 +7,7 @@ import threading
 import torch
 
 from .. import _lib, flags
-from ._base import _p, _stream, _written, _ws
+from ._base import _p, _stream, _written, _ws, activation_exponent_value, overflow_flag
 
 
 def linear_attention(q, k, v, nhead, q_mask=None, kv_mask=None, eps=1e-6):
@@ -24,6 +24,40 @@ def linear_attention(q, k, v, nhead, q_mask=None, kv_mask=None, eps=1e-6):
                                       nhead, D, _p(q_mask, torch.uint8), _p(kv_mask, torch.uint8), float(eps),
                                       _p(out), _p(ws), _stream())
     _lib.check(rc, 'far_linear_attention_f32')
+    return out
+
+def full_attention(q, k, v, nhead, q_mask=None, kv_mask=None):
+    """K22: LoFTR's full (softmax) attention core, inference only.  q: (N, L, C), k, v: (N, S, C) raw fp32 projections (heads
+    concatenated, head dim C // nhead in {16, 32}); returns (N, L, C) = softmax_s(q . k / sqrt(D)) v per head, on split-fp16 MFMAs
+    with an online softmax (the (N, L, S, H) scores never exist).  Masks (N, L) / (N, S), optional (None = all ones): a masked key
+    is selected out (non-finite k / v there never reach an output), a padded query row and every row of an image without a valid
+    key are exact zeros.  Operands are split around the thread's activation exponent; a value beyond its range ORs
+    ops.overflow_flag (check_activation_range raises)."""
+    lib = _lib.load()
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise _lib.FarHipError(f'full_attention: q (N, L, C), k, v (N, S, C); got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}')
+    N, L, C = q.shape
+    S = k.shape[1]
+    if nhead < 1 or C % nhead:
+        raise _lib.FarHipError(f'full_attention: {C} channels do not divide into {nhead} heads')
+    D = C // nhead
+    as_u8 = lambda m, n: None if m is None else m.reshape(N, n).to(torch.uint8).contiguous()
+    q_mask, kv_mask = as_u8(q_mask, L), as_u8(kv_mask, S)
+    out = torch.empty(N, L, C, dtype=torch.float32, device=q.device)
+    if D not in (16, 32):
+        raise _lib.FarHipError(f'full_attention: head dim {D} has no kernel (16 and 32 do)')
+    if N == 0 or L == 0:
+        return out
+    if S == 0:
+        return out.zero_()
+    ws = _ws(lib.far_full_attention_workspace_bytes(N, L, S, nhead, D), q.device)
+    rc = lib.far_full_attention_f16s(_p(q, torch.float32), _p(k, torch.float32), _p(v, torch.float32), N, L, S, nhead, D,
+                                     _p(q_mask, torch.uint8), _p(kv_mask, torch.uint8), activation_exponent_value(), _p(out), _p(ws),
+                                     _p(overflow_flag(q.device)), _stream())
+    _lib.check(rc, 'far_full_attention_f16s')
     return out
 
 class _LinearAttentionFn(torch.autograd.Function):

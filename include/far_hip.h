@@ -30,7 +30,7 @@ typedef struct ihipStream_t* far_stream_t; /* == hipStream_t */
 
 /* ABI version of this header; bumped when a signature changes (2: activation exponent / overflow flag of K9, K13, K14; 3: the
  * far_wino_* / far_conv3x3_wino_f32 entry points, 16 tuning keys; 4: far_upsample2x_bwd_f32, far_fine_scatter_det_f32, far_bn_train_*, far_adamw_*; 5: far_linear_kv_f16s, far_linear_q_apply_f16s,
- * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s).  far_amd/_lib.py refuses a library whose version differs. */
+ * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup).  far_amd/_lib.py refuses a library whose version differs. */
 int far_abi_version(void);
 /* Id of the sources the library was built from: sha256/16 over far_amd/csrc/* and the compiler flags (far_amd/build.py
  * source_id()).  far_amd/_lib.py refuses a library whose id differs from the sources it sits next to. */
@@ -260,6 +260,23 @@ int far_linear_attention_f32(const float* q, const float* k, const float* v, int
  * that far_linear_kv_f16s leaves (D = 32) -- the launch far_linear_attention_f32 ends with (linear_attention.py:46-50). */
 int far_linear_attention_apply_f32(const float* q, const float* kv, int N, int L, int S, int H, const uint8_t* q_mask, float eps,
                                    float* out, far_stream_t stream);
+
+/* LoFTR's full (softmax) attention core (attention = 'full', linear_attention.py:55-88; full_attention_f16s.hip), inference:
+ *   out[n, l, h, :] = sum_s softmax_s(q[n,l,h,:] . k[n,s,h,:] / sqrt(D)) v[n,s,h,:]
+ * on split-fp16 MFMAs with an online softmax over key tiles: the (N, L, S, H) score tensor never exists.  Operands as for
+ * far_linear_attention_f32: q, out [N][L][H*D], k, v [N][S][H*D] fp32 contiguous; D in {16, 32} (anything else: -22); H, L, S >= 1;
+ * N = 0 returns at once.  q_mask [N][L], kv_mask [N][S]: optional uint8, NULL = all ones.  Mask convention (a deviation from the
+ * reference, whose masked form yields NaN rows): a masked key is selected out -- its k / v values are never used,
+ * not even non-finite ones --, a padded query row is exact zeros, and so is every row of an image without a valid key.
+ * act_exp: q, k, v are multiplied by 2^act_exp before the fp16 split (4 = the default; -24 .. 8): values up to 65504 / 2^act_exp
+ * survive it.  overflow: device int or NULL, |= 1 when a value that takes part is beyond that range or not finite (out then holds
+ * inf / NaN).  No float atomics; an image's output bits do not depend on the batch it is computed in.
+ * ws: far_full_attention_workspace_bytes(N, L, S, H, D) bytes -- the partial results when the key axis is split across workgroups
+ * (short L, long S); 0 otherwise, and then ws may be NULL.  The query needs no GPU. */
+size_t far_full_attention_workspace_bytes(int N, int L, int S, int H, int D);
+int far_full_attention_f16s(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D,
+                            const uint8_t* q_mask, const uint8_t* kv_mask, int act_exp, float* out, void* ws,
+                            int* overflow, far_stream_t stream);
 
 /* K5 backward (training path): gradients of far_linear_attention_f32 w.r.t. the raw projections q, k, v given
  * g = dL/dout -- what autograd derives from linear_attention.py:31-50 in the reference.  Token-parallel kernels with the

@@ -2,8 +2,8 @@
 
 Container-only: needs /root/reference and tools/ref_shim.py.  The fixtures are data (seeds, small inputs,
 expected outputs); no reference source is copied.  Weights come from far_amd.synth (seeded), inputs from
-seeds recorded in each file.  Run:  python tools/make_goldens.py  (all of g1 ... g18 and g20; `python tools/make_goldens.py g20`
-for one; g19 comes from tools/make_golden_vit.py).  g20 = LoFTR.forward off the default launch sequence of far_amd (unequal image
+seeds recorded in each file.  Run:  python tools/make_goldens.py  (all of g1 ... g18, g20 and g21; `python tools/make_goldens.py g20`
+for one; g19 comes from tools/make_golden_vit.py).  g21 = the full softmax attention core, layer and stack (attention = 'full').  g20 = LoFTR.forward off the default launch sequence of far_amd (unequal image
 sizes, padded masks, scales), with the fp32 run's deviation from the float64 oracle stored next to it.
 """
 import importlib.util
@@ -27,6 +27,7 @@ os.makedirs(OUT, exist_ok=True)
 from far_amd import synth  # noqa: E402
 from tests.util import (GRAD_KEYS, correlated_features, loss_inputs, spvs_scene, train_inputs,  # noqa: E402
                         train_step, two_view_scene)
+from tests import full_attention_inputs as fa_in  # noqa: E402
 
 NOTE_KORNIA = ('uses tools/ref_shim.py restatements of kornia 0.7.1 (create_meshgrid / spatial_expectation2d / '
                'sampson_epipolar_distance): parity unpinned against kornia itself')
@@ -725,6 +726,67 @@ def g20_matcher_offdefault(m):
     save('g20_matcher_offdefault', **out)
 
 
+def g21_full_attention():
+    """LoFTR's FullAttention (linear_attention.py:55-88), a LoFTREncoderLayer(256, 8, 'full') and a LocalFeatureTransformer with
+    attention 'full', on the seeded inputs of tests/full_attention_inputs.py.  Per case: the fp32 outputs (rows at a fixed stride)
+    and dev32_<case> = the maximum deviation of the fp32 run from the SAME reference code run in float64.  The masked core case is
+    compared on valid query rows (the reference's padded rows are NaN); the masked stack has no golden because the reference
+    returns NaN there -- asserted here, so that the stated deviation of far_amd's mask convention stays pinned to it."""
+    import copy
+    from src.loftr.loftr_module.linear_attention import FullAttention
+    from src.loftr.loftr_module.transformer import LocalFeatureTransformer, LoFTREncoderLayer
+    from tests.util import masked_coarse_inputs
+    out = {}
+    att = FullAttention().eval()
+    with torch.no_grad():
+        for name, c in fa_in.CASES.items():
+            inp = fa_in.core_inputs(name)
+            H, D = inp['H'], inp['D']
+            t = {k: torch.from_numpy(inp[k]) for k in ('q', 'k', 'v')}
+            qm = None if inp['q_mask'] is None else torch.from_numpy(inp['q_mask'])
+            km = None if inp['kv_mask'] is None else torch.from_numpy(inp['kv_mask'])
+            heads = lambda x: x.view(x.shape[0], x.shape[1], H, D)
+            y32 = att(heads(t['q']), heads(t['k']), heads(t['v']), qm, km).reshape(t['q'].shape)
+            y64 = att(heads(t['q'].double()), heads(t['k'].double()), heads(t['v'].double()), qm, km).reshape(t['q'].shape)
+            if qm is not None:
+                assert bool(torch.isnan(y32[~qm]).all()) and bool(torch.isfinite(y32[qm]).all())   # the reference: NaN on padded rows
+                y32 = torch.where(qm[..., None], y32, torch.zeros_like(y32))
+                y64 = torch.where(qm[..., None], y64, torch.zeros_like(y64))
+            out['out_' + name] = fa_in.strided_rows(y32.numpy(), c['stride'])
+            out['dev32_' + name] = np.float64((y32.double() - y64).abs().max())
+            scores = torch.einsum('nlhd,nshd->nlsh', heads(t['q']), heads(t['k'])) / D ** 0.5
+            out['maxscore_' + name] = np.float64(scores.abs().max())
+            print(f'g21 {name}: dev32 {out["dev32_" + name]:.3e}  max|score| {out["maxscore_" + name]:.1f}  max|out| {float(y32.abs().max()):.3f}')
+        # (e) one encoder layer
+        layer = fa_in.seeded_fill(LoFTREncoderLayer(256, fa_in.NHEAD, 'full'), fa_in.LAYER['seed']).eval()
+        x, src = (torch.from_numpy(a) for a in fa_in.layer_inputs())
+        y32 = layer(x, src)
+        y64 = copy.deepcopy(layer).double()(x.double(), src.double())
+        out['out_layer'] = fa_in.strided_rows(y32.numpy(), fa_in.LAYER['stride'])
+        out['dev32_layer'] = np.float64((y32.double() - y64).abs().max())
+        # (f) the stack
+        stack = fa_in.seeded_fill(LocalFeatureTransformer(copy.deepcopy(fa_in.STACK['config'])), fa_in.STACK['seed']).eval()
+        f0, f1 = (torch.from_numpy(a) for a in fa_in.stack_inputs())
+        a32, b32 = stack(f0, f1)
+        a64, b64 = copy.deepcopy(stack).double()(f0.double(), f1.double())
+        out['out_stack0'] = fa_in.strided_rows(a32.numpy(), fa_in.STACK['stride'])
+        out['out_stack1'] = fa_in.strided_rows(b32.numpy(), fa_in.STACK['stride'])
+        out['dev32_stack'] = np.float64(max((a32.double() - a64).abs().max(), (b32.double() - b64).abs().max()))
+        print(f'g21 layer: dev32 {out["dev32_layer"]:.3e}   stack: dev32 {out["dev32_stack"]:.3e}')
+        # the masked stack: the reference's padded query rows are NaN after the first layer and poison every row of the image
+        mi = masked_coarse_inputs()
+        m0, m1 = (torch.from_numpy(mi[k]).flatten(-2) for k in ('mask0', 'mask1'))
+        a, b = stack(torch.from_numpy(mi['f0']), torch.from_numpy(mi['f1']), m0, m1)
+        assert bool(torch.isnan(a[m0]).any()) and bool(torch.isnan(b[m1]).any()), 'the reference no longer returns NaN on a masked stack'
+        out['ref_masked_stack_nan'] = np.bool_(True)
+        try:                                              # kv_mask without q_mask: the reference raises
+            att(torch.zeros(1, 4, 1, 16), torch.zeros(1, 4, 1, 16), torch.zeros(1, 4, 1, 16), None, torch.ones(1, 4, dtype=torch.bool))
+            raise AssertionError('the reference accepted kv_mask without q_mask')
+        except TypeError:
+            out['ref_kv_mask_alone_raises'] = np.bool_(True)
+    save('g21_full_attention', **out)
+
+
 def g8_manifest(m):
     man = {k: list(v.shape) for k, v in m.state_dict().items()}
     with open(os.path.join(OUT, 'g8_state_dict_manifest.json'), 'w') as f:
@@ -768,6 +830,9 @@ if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'g17':
         g17_fivepoint()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'g21':
+        g21_full_attention()
+        sys.exit(0)
     g1_coarse()
     g9_metrics()
     g5_solver()
@@ -788,3 +853,4 @@ if __name__ == '__main__':
     g17_fivepoint()
     g18_masked_training_coarse()
     g20_matcher_offdefault(ref_model()[0])
+    g21_full_attention()
