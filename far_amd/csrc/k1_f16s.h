@@ -130,3 +130,10 @@ __device__ __forceinline__ void score_tile(f32x16 (&acc)[2], const unsigned char
 }
 
 }  // namespace
+
+// sinkhorn_f16s.hip -> sinkhorn_train_f16s.hip (library-internal, not part of the C ABI): the matcher's operand preparation and its T
+// iterations (the same k_skh_stats launches: the bits of inference) with every (u^t, v^t) kept.  uh [(T+1)][Z][Lp], vh [(T+1)][Z][Sp],
+// binh [(T+1)][2][Z] (U_L, V_S) in log2 units; slice 0 is u = v = 0
+int far_skh_history_launch(const float* f0, const float* f1, int Z, int L, int S, const float* bin_score, int iters,
+                           const uint8_t* mask0, const uint8_t* mask1, _Float16* ah, _Float16* al, _Float16* bh, _Float16* bl,
+                           float* uh, float* vh, float* binh, int* overflow, hipStream_t stream);

@@ -384,3 +384,32 @@ int far_coarse_match_sinkhorn_f16s(const float* f0, const float* f1, int Z, int 
 }
 
 }  // extern "C"
+
+// ---- glue with sinkhorn_train_f16s.hip (declared in k1_f16s.h): it lives here because it launches this file's k_skh_stats, so that
+// the training forward runs the very kernels of inference ----
+int far_skh_history_launch(const float* f0, const float* f1, int Z, int L, int S, const float* bin_score, int iters,
+                           const uint8_t* mask0, const uint8_t* mask1, _Float16* ah, _Float16* al, _Float16* bh, _Float16* bl,
+                           float* uh, float* vh, float* binh, int* overflow, hipStream_t stream) {
+    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const float c1 = (float)(1.4426950408889634 / ((double)C * PRESCALE * PRESCALE));
+    const double n2 = -std::log2((double)L + (double)S);
+    const float nrm = (float)n2, lmu_l = (float)(std::log2((double)S) + n2), lnu_s = (float)(std::log2((double)L) + n2);
+    auto gridp = [](long n) { long b = (n + 255) / 256; return (unsigned)(b < 65536L * 4 ? b : 65536L * 4); };
+    hipLaunchKernelGGL(k1_prep, dim3(gridp((long)Z * Lp * 32)), dim3(256), 0, stream, f0, Z, L, Lp, ah, al, overflow, (unsigned*)nullptr);
+    hipLaunchKernelGGL(k1_prep, dim3(gridp((long)Z * Sp * 32)), dim3(256), 0, stream, f1, Z, S, Sp, bh, bl, overflow, (unsigned*)nullptr);
+    hipLaunchKernelGGL(k_skh_init, dim3(gridp((long)Z * (Lp + Sp))), dim3(256), 0, stream, uh, L, Lp, vh, S, Sp, binh, Z);
+    const size_t smem_s = 2 * TILE_PLANE + (KT + 8) * sizeof(float);
+    FAR_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)k_skh_stats<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_s));
+    const size_t nu = (size_t)Z * Lp, nv = (size_t)Z * Sp;
+    for (int t = 1; t <= iters; ++t) {
+        float* const bt = binh + (size_t)t * 2 * Z;
+        const float* const bp = binh + (size_t)(t - 1) * 2 * Z;
+        hipLaunchKernelGGL(k_skh_stats<true>, dim3((Lp / 128) * Z), dim3(256), smem_s, stream, ah, al, bh, bl, Z, L, S, Lp, Sp, c1,
+                           mask0, mask1, (const float*)(vh + (t - 1) * nv), bp + Z, bin_score, nrm, lmu_l, uh + t * nu, bt,
+                           (float*)nullptr);
+        hipLaunchKernelGGL(k_skh_stats<true>, dim3((Sp / 128) * Z), dim3(256), smem_s, stream, bh, bl, ah, al, Z, S, L, Sp, Lp, c1,
+                           mask1, mask0, (const float*)(uh + t * nu), (const float*)bt, bin_score, nrm, lnu_s, vh + t * nv, bt + Z,
+                           (float*)nullptr);
+    }
+    return far_check_launch();
+}

@@ -37,7 +37,7 @@ class CoarseMatching(nn.Module):
         self.match_type = config['match_type']
         if self.match_type == 'sinkhorn':
             # optimal transport with a learned dustbin score (coarse_matching.py:73-82; the loftr_ot* configurations): inference on
-            # far_coarse_match_sinkhorn_f16s; training through it (backward, dustbin-supervised loss) is not built
+            # far_coarse_match_sinkhorn_f16s; training through it on far_sinkhorn_pos_conf_f16s / _bwd_f16 (ops.sinkhorn_pos_conf)
             self.bin_score = nn.Parameter(torch.tensor(config['skh_init_bin_score'], requires_grad=True))
             self.skh_iters = config['skh_iters']
             self.skh_prefilter = config['skh_prefilter']
@@ -109,11 +109,26 @@ class CoarseMatching(nn.Module):
                             m1.sum(1).max(-1)[0], m1.sum(-1).max(-1)[0]], 1).to(torch.int32).contiguous()
 
     def _forward_sinkhorn(self, feat_c0, feat_c1, data, mask_c0=None, mask_c1=None, overlap=None):
-        """match_type 'sinkhorn' in evaluation mode (coarse_matching.py:120-147): the same data keys as the dual-softmax
-        evaluation path, plus conf_matrix_with_bin when materialize_conf is set (conf_matrix is then its [:, :L, :S] view)."""
-        if self.training or ag.needs_grad(feat_c0, feat_c1):
-            raise NotImplementedError('Sinkhorn coarse matching: training / gradients through the optimal-transport matcher are not '
-                                      'built (inference only)')
+        """match_type 'sinkhorn' (coarse_matching.py:120-147).  Evaluation: the same data keys as the dual-softmax evaluation path, plus
+        conf_matrix_with_bin when materialize_conf is set (conf_matrix is then its [:, :L, :S] view).  Training (or gradients needed) on
+        GPU tensors with the sparse labels spv_b/i/j_ids in data: the `if train:` branch below (conf_matrix None; conf_pos, conf_bin0,
+        conf_bin1 from ops.sinkhorn_pos_conf).  Evaluation with the labels in data (val_step): the same three keys, no graph."""
+        train = self.training or ag.needs_grad(feat_c0, feat_c1)
+        if train:
+            if not feat_c0.is_cuda:
+                raise NotImplementedError('Sinkhorn coarse matching: training / gradients through the optimal-transport matcher exist '
+                                          'on the GPU only (no differentiable form off it)')
+            if 'spv_b_ids' not in data or not self.config.get('sparse_spvs', True):
+                raise NotImplementedError('Sinkhorn coarse matching: training needs the sparse labels spv_b_ids / spv_i_ids / spv_j_ids '
+                                          'in data (dense supervision is not built)')
+            if self.materialize_conf:
+                raise NotImplementedError('Sinkhorn coarse matching: training never builds the dense conf_matrix_with_bin '
+                                          '(materialize_conf is for evaluation)')
+            if self.skh_prefilter and not self.training:
+                # the reference's loss would read the FILTERED matrix there (its gradient through the in-place filter), while
+                # ops.sinkhorn_pos_conf differentiates the unfiltered one
+                raise NotImplementedError('Sinkhorn coarse matching: gradients in evaluation mode with skh_prefilter are not built '
+                                          '(the prefilter is off in training mode; run validation under no_grad)')
         if not feat_c0.is_cuda:
             ag.require('Sinkhorn CoarseMatching on CPU tensors')
         if self.bf16:
@@ -128,10 +143,48 @@ class CoarseMatching(nn.Module):
         scale = data['hw0_i'][0] / data['hw0_c'][0]
         s0 = data['scale0'].float().contiguous() if 'scale0' in data else None
         s1 = data['scale1'].float().contiguous() if 'scale1' in data else None
+        if train:
+            # The sparse loss of this configuration (loftr_loss.py:86-119) reads the coupling matrix at the ground-truth positions and
+            # at its dustbin column / row only, so no (N, L+1, S+1) tensor is built: the matcher selects the predicted matches under
+            # no_grad (as the reference's get_coarse_match; the prefilter is off in training, coarse_matching.py:135) and
+            # ops.sinkhorn_pos_conf gives the differentiable entries with a HIP backward to both feature maps and bin_score.
+            if overlap is not None:
+                overlap()
+            with torch.no_grad():
+                out = ops.coarse_match_sinkhorn(feat_c0.detach().float().contiguous(), feat_c1.detach().float().contiguous(),
+                                                self.bin_score, self.skh_iters, self.thr, self.border_rm, data['hw0_c'], data['hw1_c'],
+                                                scale, as_u8(mask_c0), as_u8(mask_c1), self._valid_hw(data), None, None,
+                                                prefilter=False)
+                picked = self._sample_train(out['b_ids'], out['i_ids'], out['j_ids'], out['mconf'], data, feat_c0.shape[0])
+            pos, bin0, bin1 = ops.sinkhorn_pos_conf(feat_c0, feat_c1, self.bin_score, self.skh_iters, data['spv_b_ids'],
+                                                    data['spv_i_ids'], data['spv_j_ids'], as_u8(mask_c0), as_u8(mask_c1))
+            data.update({'conf_matrix': None, 'conf_pos': pos, 'conf_bin0': bin0, 'conf_bin1': bin1})
+            data.pop('conf_matrix_with_bin', None)
+            data.update(**picked)
+            return
+        spv = 'spv_b_ids' in data and not self.materialize_conf
         out = ops.coarse_match_sinkhorn(feat_c0.float().contiguous(), feat_c1.float().contiguous(), self.bin_score, self.skh_iters,
                                         self.thr, self.border_rm, data['hw0_c'], data['hw1_c'], scale, as_u8(mask_c0),
                                         as_u8(mask_c1), self._valid_hw(data), s0, s1, prefilter=self.skh_prefilter,
-                                        want_conf=self.materialize_conf, overlap=overlap)
+                                        want_conf=self.materialize_conf or (spv and self.skh_prefilter), overlap=overlap)
+        if spv:
+            # validation (the matcher in eval mode, then the loss): the three groups of entries the loss reads, no graph.  With the
+            # prefilter the loss sees the filtered matrix (the reference clones conf_matrix_with_bin after the in-place filter,
+            # coarse_matching.py:135-142): the positions are read from the matcher's own filtered output
+            with torch.no_grad():
+                if self.skh_prefilter:
+                    cw = out['conf_matrix_with_bin']
+                    data.update({'conf_pos': cw[data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids']],
+                                 'conf_bin0': cw[:, :-1, -1].contiguous(), 'conf_bin1': cw[:, -1, :-1].contiguous()})
+                    out['conf_matrix'] = out['conf_matrix_with_bin'] = None
+                else:
+                    pos, bin0, bin1 = ops.sinkhorn_pos_conf(feat_c0.float().contiguous(), feat_c1.float().contiguous(), self.bin_score,
+                                                            self.skh_iters, data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids'],
+                                                            as_u8(mask_c0), as_u8(mask_c1))
+                    data.update({'conf_pos': pos, 'conf_bin0': bin0, 'conf_bin1': bin1})
+        else:
+            for k in ('conf_pos', 'conf_bin0', 'conf_bin1'):
+                data.pop(k, None)
         mconf = out['mconf']
         data.update({
             'conf_matrix': out['conf_matrix'],
@@ -145,7 +198,6 @@ class CoarseMatching(nn.Module):
             data['conf_matrix_with_bin'] = out['conf_matrix_with_bin']
         else:
             data.pop('conf_matrix_with_bin', None)
-        data.pop('conf_pos', None)          # the validation branch's sparse dual-softmax confidences do not apply
 
     # ------------------------------------------------------------------------------------------------------
     # training (coarse_matching.py:86-147 + :199-240).  The coarse loss of this configuration (dual-softmax, sparse

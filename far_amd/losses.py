@@ -57,6 +57,67 @@ def coarse_focal_loss(data, alpha=FOCAL_ALPHA, gamma=FOCAL_GAMMA, pos_weight=POS
     return pos_weight * loss_pos.mean()                                        # :111-112
 
 
+NEG_WEIGHT = 1.0
+
+
+def sinkhorn_loss_entries(data):
+    """The entries of the optimal-transport coupling matrix that the sparse loss reads (loftr_loss.py:92, :98-99):
+    -> (pos (M,), bin0 (N, L) = P[:, :L, S], bin1 (N, S) = P[:, L, :S], (b, i, j) of the positives, no_gt).
+    GPU training / validation path: data['conf_pos'] / ['conf_bin0'] / ['conf_bin1'] (ops.sinkhorn_pos_conf) at spv_b/i/j_ids;
+    otherwise a dense data['conf_matrix_with_bin'] (N, L+1, S+1) is indexed, the positives given as spv ids or as conf_matrix_gt.
+    no_gt (:65-70): not one ground-truth match -- the positives are then the single dummy entry (0, 0, 0)."""
+    if data.get('conf_pos') is not None and data.get('conf_bin0') is not None:
+        ids = data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids']
+        return data['conf_pos'], data['conf_bin0'], data['conf_bin1'], ids, has_no_ground_truth(data)
+    cw = data['conf_matrix_with_bin']
+    if 'spv_b_ids' in data:
+        ids = data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids']
+        no_gt = has_no_ground_truth(data)
+    else:
+        ids = torch.where(data['conf_matrix_gt'] == 1)
+        no_gt = ids[0].numel() == 0
+    if ids[0].numel() == 0:
+        ids = tuple(torch.zeros(1, dtype=torch.long, device=cw.device) for _ in range(3))
+    return cw[:, :-1, :-1][ids], cw[:, :-1, -1], cw[:, -1, :-1], ids, no_gt
+
+
+def coarse_focal_loss_sinkhorn(data, alpha=FOCAL_ALPHA, gamma=FOCAL_GAMMA, pos_weight=POS_WEIGHT, neg_weight=NEG_WEIGHT):
+    """loftr_loss.py:56-119 for sparse_spvs + match_type 'sinkhorn' + focal: the positive term at the ground-truth positions, the
+    negative term on the dustbin entries of the rows / columns WITHOUT ground truth (the dustbin should take their mass: the same
+    focal form on P[:, i, S] and P[:, L, j]).  Padded masks (data['mask0'] / ['mask1'], compute_c_weight :190-196 with
+    weight = mask0 x mask1): the positive terms are weighted, and a negative stays only when its row / column of the weight is not
+    all zero (:106-114).  No ground truth at all (:65-70): the dummy positive gets weight 0 and c_pos_w = 0; every row and column
+    is a negative."""
+    pos, bin0, bin1, (b, i, j), no_gt = sinkhorn_loss_entries(data)
+    focal = lambda p: -alpha * torch.pow(1 - p, gamma) * p.log()                               # :95, :100
+    neg0 = torch.ones(bin0.shape, dtype=torch.bool, device=bin0.device)                        # :98  conf_gt.sum(-1) == 0
+    neg1 = torch.ones(bin1.shape, dtype=torch.bool, device=bin1.device)                        #      conf_gt.sum(1) == 0
+    if not no_gt:
+        neg0[b, i] = False
+        neg1[b, j] = False
+    else:
+        pos_weight = 0.                                                                        # :70
+    loss_pos = focal(torch.clamp(pos, 1e-6, 1 - 1e-6))                                         # :87, :95
+    loss_neg = focal(torch.clamp(torch.cat([bin0[neg0], bin1[neg1]], 0), 1e-6, 1 - 1e-6))      # :99-100
+    if 'mask0' in data:                                                                        # :106-114
+        with torch.no_grad():
+            m0 = data['mask0'].flatten(-2).float()
+            m1 = data['mask1'].flatten(-2).float()
+            w_pos = m0[b, i] * m1[b, j]
+            rows = m0 * m1.sum(-1, keepdim=True)                                               # weight.sum(-1)
+            cols = m1 * m0.sum(-1, keepdim=True)                                               # weight.sum(1)
+            if no_gt:                                                                          # :68-69  weight[0, 0, 0] = 0
+                w_pos = torch.zeros_like(w_pos)
+                rows[0, 0] -= m0[0, 0] * m1[0, 0]
+                cols[0, 0] -= m0[0, 0] * m1[0, 0]
+            keep = torch.cat([(rows != 0)[neg0], (cols != 0)[neg1]], 0)
+        loss_pos = loss_pos * w_pos
+        loss_neg = loss_neg[keep]
+    # an empty conf_pos (M = 0 labels, no dummy entry): the dummy positive's term is 0 x finite, so the term and its gradient vanish
+    term_pos = pos_weight * loss_pos.mean() if pos.numel() else pos.sum() * 0.0
+    return term_pos + neg_weight * loss_neg.mean()                                             # :116
+
+
 def fine_loss_l2_std(expec_f, expec_f_gt, correct_thr=1.0, training=True):
     """loftr_loss.py:151-183 (fine_type 'l2_with_std').  expec_f (M, 3) <x, y, std>, expec_f_gt (M, 2).  Returns None in
     eval mode when no coarse match is correct (:171-172)."""
@@ -107,11 +168,14 @@ class LoFTRLoss(torch.nn.Module):
         self.config = config
         lc = self.loss_config = config['loftr']['loss']
         mc = config['loftr']['match_coarse']
-        if mc['match_type'] != 'dual_softmax' or lc['coarse_type'] != 'focal' or not mc.get('sparse_spvs', True):
-            raise NotImplementedError('far_amd.losses.LoFTRLoss covers dual_softmax + focal + sparse supervision '
-                                      '(the FAR training scripts); sinkhorn / cross-entropy / dense supervision are not built')
+        if mc['match_type'] not in ('dual_softmax', 'sinkhorn') or lc['coarse_type'] != 'focal' or not mc.get('sparse_spvs', True):
+            raise NotImplementedError('far_amd.losses.LoFTRLoss covers dual_softmax / sinkhorn + focal + sparse supervision '
+                                      '(the FAR training scripts, the loftr_ot configurations); cross-entropy / dense supervision '
+                                      'are not built')
+        self.match_type = mc['match_type']
         self.correct_thr = lc['fine_correct_thr']
         self.c_pos_w = lc['pos_weight']
+        self.c_neg_w = lc.get('neg_weight', NEG_WEIGHT)
         self.fine_type = lc['fine_type']
 
     @torch.no_grad()
@@ -126,16 +190,19 @@ class LoFTRLoss(torch.nn.Module):
     def forward(self, data):
         cfg = self.config
         lc = self.loss_config
-        ref = data['conf_pos'] if data.get('conf_pos') is not None else data.get('conf_matrix')
+        ref = next((data[k] for k in ('conf_pos', 'conf_matrix', 'conf_matrix_with_bin') if data.get(k) is not None), None)
         dev = ref.device if ref is not None else data['expec_rt'].device
         loss = torch.zeros(1, device=dev)                                                      # :303
         scalars = {}
         if cfg['loftr'].get('from_saved_preds') is None and not cfg.get('use_correspondence_transformer', False):
             d = data
-            if data.get('conf_pos') is None and 'spv_b_ids' not in data:                       # dense drop-in use: positions from conf_matrix_gt
-                b, i, j = torch.where(data['conf_matrix_gt'] == 1)
-                d = dict(data, spv_b_ids=b, spv_i_ids=i, spv_j_ids=j, spv_gt_count=int(b.numel()))
-            loss_c = coarse_focal_loss(d, lc['focal_alpha'], lc['focal_gamma'], self.c_pos_w, weight=self.compute_c_weight(d))
+            if self.match_type == 'sinkhorn':
+                loss_c = coarse_focal_loss_sinkhorn(data, lc['focal_alpha'], lc['focal_gamma'], self.c_pos_w, self.c_neg_w)
+            else:
+                if data.get('conf_pos') is None and 'spv_b_ids' not in data:                   # dense drop-in use: positions from conf_matrix_gt
+                    b, i, j = torch.where(data['conf_matrix_gt'] == 1)
+                    d = dict(data, spv_b_ids=b, spv_i_ids=i, spv_j_ids=j, spv_gt_count=int(b.numel()))
+                loss_c = coarse_focal_loss(d, lc['focal_alpha'], lc['focal_gamma'], self.c_pos_w, weight=self.compute_c_weight(d))
             loss = loss + loss_c * lc['coarse_weight']                                         # :314
             scalars['loss_c'] = loss_c.detach().cpu()
             fn = fine_loss_l2_std if self.fine_type == 'l2_with_std' else fine_loss_l2

@@ -191,6 +191,79 @@ class _CoarsePosConf(torch.autograd.Function):
         _lib.check(rc, 'far_coarse_pos_conf_bwd_f16')
         return df0, df1, None, None, None, None
 
+SINKHORN_MAX_ITERS = 48          # far_sinkhorn_pos_conf_*: the 2T terms of a column tile are staged in LDS
+
+
+class _SinkhornPosConf(torch.autograd.Function):
+    """The optimal-transport coupling matrix at M given positions and at its dustbin column / row, differentiable w.r.t. both
+    coarse feature maps and bin_score, without the dense matrix (far_sinkhorn_pos_conf_f16s / far_sinkhorn_pos_conf_bwd_f16)."""
+
+    @staticmethod
+    def forward(ctx, f0, f1, bin_score, pb, pi, pj, mask0, mask1, iters):
+        lib = _lib.load()
+        Z, L, C = f0.shape
+        S = f1.shape[1]
+        dev = f0.device
+        f0c, f1c = f0.detach().float().contiguous(), f1.detach().float().contiguous()
+        bs = bin_score.detach().float().contiguous()
+        pb, pi, pj = (t.to(torch.int64).contiguous() for t in (pb, pi, pj))
+        m0 = None if mask0 is None else mask0.reshape(Z, L).to(torch.uint8).contiguous()
+        m1 = None if mask1 is None else mask1.reshape(Z, S).to(torch.uint8).contiguous()
+        M = int(pb.numel())
+        ws = _ws(lib.far_sinkhorn_pos_conf_workspace_bytes(Z, L, S, C, iters), dev)
+        p = torch.empty(M, dtype=torch.float32, device=dev)
+        bin0 = torch.empty(Z, L, dtype=torch.float32, device=dev)
+        bin1 = torch.empty(Z, S, dtype=torch.float32, device=dev)
+        rc = lib.far_sinkhorn_pos_conf_f16s(_p(f0c, torch.float32), _p(f1c, torch.float32), Z, L, S, C, _p(bs, torch.float32), iters,
+                                            _p(m0), _p(m1), _p(pb), _p(pi), _p(pj), M, _p(p), _p(bin0), _p(bin1), _p(ws),
+                                            _p(overflow_flag(dev)), _stream())
+        _lib.check(rc, 'far_sinkhorn_pos_conf_f16s')
+        ctx.save_for_backward(f0c, f1c, bs, pb, pi, pj, p, bin0, bin1, ws)
+        ctx.masks = (m0, m1)
+        ctx.iters = iters
+        ctx.bin_shape = bin_score.shape
+        return p, bin0, bin1
+
+    @staticmethod
+    def backward(ctx, g_pos, g_bin0, g_bin1):
+        lib = _lib.load()
+        f0c, f1c, bs, pb, pi, pj, p, bin0, bin1, ws = ctx.saved_tensors
+        m0, m1 = ctx.masks
+        Z, L, C = f0c.shape
+        S = f1c.shape[1]
+        # dL/dp * p = dL/dlogP: bounded for the focal loss even where p -> 0
+        w = lambda g, q: torch.zeros_like(q) if g is None else (g.float() * q).contiguous()
+        wp, w0, w1 = w(g_pos, p), w(g_bin0, bin0), w(g_bin1, bin1)
+        df0, df1 = torch.empty_like(f0c), torch.empty_like(f1c)
+        dbin = torch.empty(1, dtype=torch.float32, device=f0c.device)
+        rc = lib.far_sinkhorn_pos_conf_bwd_f16(_p(f0c), _p(f1c), Z, L, S, C, _p(bs), ctx.iters, _p(m0), _p(m1), _p(pb), _p(pi), _p(pj),
+                                               int(pb.numel()), _p(wp, torch.float32), _p(w0, torch.float32), _p(w1, torch.float32),
+                                               _p(df0), _p(df1), _p(dbin), _p(ws), _stream())
+        _lib.check(rc, 'far_sinkhorn_pos_conf_bwd_f16')
+        return df0, df1, dbin.reshape(ctx.bin_shape), None, None, None, None, None, None
+
+
+def sinkhorn_pos_conf(f0, f1, bin_score, iters, pb, pi, pj, mask0=None, mask1=None):
+    """The optimal-transport matcher on the training path: (conf_pos (M,), conf_bin0 (Z, L), conf_bin1 (Z, S)) = the coupling matrix
+    exp(log_assign) of ops.coarse_match_sinkhorn (no prefilter) at the positions (pb, pi, pj), its dustbin column [:, :L, S] and its
+    dustbin row [:, L, :S] -- what the sparse loss reads (loftr_loss.py:86-119) -- with a HIP backward to f0, f1 and bin_score (the
+    gradient of the unrolled iterations).  mask0 (Z, L) / mask1 (Z, S): padded-mask batches.  C must be 256, iters <= 48."""
+    if not (f0.is_cuda and f1.is_cuda and bin_score.is_cuda):
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    Z, L, C = f0.shape
+    S = f1.shape[1]
+    iters = int(iters)
+    if C != 256:
+        raise NotImplementedError('the Sinkhorn coarse matcher has kernels for C = 256 only')
+    if not 0 <= iters <= SINKHORN_MAX_ITERS:
+        raise NotImplementedError(f'training through the Sinkhorn matcher is built for 0 <= skh_iters <= {SINKHORN_MAX_ITERS}')
+    if Z == 0 or L == 0 or S == 0:         # nothing to launch: empty results that still hang in the graph
+        zero = (f0.sum() + f1.sum() + bin_score.sum()) * 0.0
+        return (torch.zeros(int(pb.numel()), device=f0.device) + zero, torch.zeros(Z, L, device=f0.device) + zero,
+                torch.zeros(Z, S, device=f0.device) + zero)
+    return _SinkhornPosConf.apply(f0, f1, bin_score, pb, pi, pj, mask0, mask1, iters)
+
+
 def coarse_pos_conf(f0, f1, pb, pi, pj, temperature):
     """K1, training: conf_matrix[pb, pi, pj] (M,) fp32 with a HIP backward to both feature maps; C must be 256."""
     if not f0.is_cuda:

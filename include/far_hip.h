@@ -172,6 +172,27 @@ int far_coarse_pos_conf_bwd_f16(const float* f0, const float* f1, int Z, int L, 
                                 const int64_t* pb, const int64_t* pi, const int64_t* pj, int M, const float* w,
                                 float* df0, float* df1, void* ws, far_stream_t stream);
 
+/* The optimal-transport matcher on the training path (sinkhorn_train_f16s.hip): the sparse loss of match_type 'sinkhorn'
+ * (src/losses/loftr_loss.py:86-119) reads the coupling matrix P = exp(log_assign) at the M ground-truth positions and at the
+ * dustbin entries P[:, i, S], P[:, L, j] only; no (Z, L+1, S+1) tensor is built.  Arguments as far_coarse_match_sinkhorn_f16s
+ * (bin_score: one device float; mask0 (Z, L) / mask1 (Z, S) optional; iters <= 48) and far_coarse_pos_conf_f16s (positions).
+ * ws: far_sinkhorn_pos_conf_workspace_bytes(Z, L, S, C, iters) bytes (0: unsupported shape), kept untouched between the forward and the backward call.
+ * forward: the matcher's own iterations (same bits as inference) with every potential kept; conf_pos[k] = P[pb[k], pi[k], pj[k]]
+ * (0 on a masked cell), conf_bin0 (Z, L) = P[:, :L, S], conf_bin1 (Z, S) = P[:, L, :S]. */
+size_t far_sinkhorn_pos_conf_workspace_bytes(int Z, int L, int S, int C, int iters);
+int far_sinkhorn_pos_conf_f16s(const float* f0, const float* f1, int Z, int L, int S, int C, const float* bin_score, int iters,
+                               const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj,
+                               int M, float* conf_pos, float* conf_bin0, float* conf_bin1, void* ws, int* overflow,
+                               far_stream_t stream);
+/* backward: the gradient of the unrolled iterations.  w_pos (M), w_bin0 (Z, L), w_bin1 (Z, S) = dL/dp * p of the three groups of
+ * entries.  df0 (Z, L, C), df1 (Z, S, C) and dbin (one float: dL/d bin_score) are overwritten.  Masked rows get exactly 0.
+ * Adjoint passes on split-fp16 scores / fp32; the two gradient contractions on plain fp16 operands (gradient-grade, as K1's);
+ * no float atomics: the same bits at every launch. */
+int far_sinkhorn_pos_conf_bwd_f16(const float* f0, const float* f1, int Z, int L, int S, int C, const float* bin_score, int iters,
+                                  const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj,
+                                  int M, const float* w_pos, const float* w_bin0, const float* w_bin1, float* df0, float* df1,
+                                  float* dbin, void* ws, far_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * K2  EMM head: bilinear dual-softmax attention  F = v~^T (softmax_row(s) * softmax_col(s)) v~
  * replaces src/loftr/loftr_module/transformer.py:275-292 (CrossAttention.forward), one call per direction

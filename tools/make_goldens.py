@@ -2,7 +2,7 @@
 
 Container-only: needs /root/reference and tools/ref_shim.py.  The fixtures are data (seeds, small inputs,
 expected outputs); no reference source is copied.  Weights come from far_amd.synth (seeded), inputs from
-seeds recorded in each file.  Run:  python tools/make_goldens.py  (all of g1 ... g18, g20 and g21; `python tools/make_goldens.py g20`
+seeds recorded in each file.  Run:  python tools/make_goldens.py  (all of g1 ... g18, g20, g21 and g22; `python tools/make_goldens.py g20`
 for one; g19 comes from tools/make_golden_vit.py).  g21 = the full softmax attention core, layer and stack (attention = 'full').  g20 = LoFTR.forward off the default launch sequence of far_amd (unequal image
 sizes, padded masks, scales), with the fp32 run's deviation from the float64 oracle stored next to it.
 """
@@ -787,6 +787,47 @@ def g21_full_attention():
     save('g21_full_attention', **out)
 
 
+def g22_sinkhorn_loss():
+    """LoFTRLoss.compute_coarse_loss (loftr_loss.py:56-119) of the reference on its sinkhorn branch (sparse supervision, focal): a
+    small dense conf_matrix_with_bin (2, L+1, S+1) with entries beyond both clamps, with and without the padded-mask weight, with a
+    pair that has no ground truth, and with no ground truth at all (:65-70).  Inputs and outputs only."""
+    from src.losses.loftr_loss import LoFTRLoss
+    from far_amd.config import far_train_config
+    cfg = far_train_config()
+    cfg['loftr']['match_coarse']['match_type'] = 'sinkhorn'
+    cfg['loftr']['loss']['neg_weight'] = 0.7
+    lf = LoFTRLoss(cfg).train()
+    rng = np.random.default_rng(122)
+    N, hw0, hw1 = 2, (6, 8), (6, 7)
+    L, S = hw0[0] * hw0[1], hw1[0] * hw1[1]
+    conf = (rng.random((N, L + 1, S + 1)) ** 4).astype(np.float32)
+    conf[rng.random(conf.shape) < 0.02] = 0.0
+    conf[rng.random(conf.shape) < 0.02] = 1.0
+    gt = np.zeros((N, L, S), np.float32)
+    for n in range(N):
+        k = 17 + 3 * n
+        gt[n, rng.permutation(L)[:k], rng.permutation(S)[:k]] = 1.0
+    for n in range(N):                                   # confident true matches, as a trained matcher gives
+        ii, jj = np.nonzero(gt[n])
+        conf[n, ii[::2], jj[::2]] = (0.5 + 0.5 * rng.random(len(ii[::2]))).astype(np.float32)
+    m0 = np.zeros((N,) + hw0, bool)
+    m1 = np.zeros((N,) + hw1, bool)
+    m0[0, :5, :8] = True; m0[1, :6, :6] = True
+    m1[0, :6, :5] = True; m1[1, :4, :7] = True
+    weight = (m0.reshape(N, L)[..., None] * m1.reshape(N, S)[:, None]).astype(np.float32)
+    gt_pair = gt.copy()
+    gt_pair[1] = 0
+    out = {}
+    for tag, g, w in (('plain', gt, None), ('weight', gt, weight), ('nogt_pair', gt_pair, None), ('nogt_pair_weight', gt_pair, weight),
+                      ('nogt', np.zeros_like(gt), None), ('nogt_weight', np.zeros_like(gt), weight)):
+        loss = lf.compute_coarse_loss(torch.from_numpy(conf.copy()), torch.from_numpy(g.copy()),
+                                      None if w is None else torch.from_numpy(w.copy()))
+        out['loss_' + tag] = loss.numpy()
+    save('g22_sinkhorn_loss', seed=122, neg_weight=np.float32(0.7), conf=conf, gt=gt.astype(np.int8), gt_pair=gt_pair.astype(np.int8),
+         mask0=m0, mask1=m1, **out)
+    print('g22:', {k: float(v) for k, v in out.items()})
+
+
 def g8_manifest(m):
     man = {k: list(v.shape) for k, v in m.state_dict().items()}
     with open(os.path.join(OUT, 'g8_state_dict_manifest.json'), 'w') as f:
@@ -833,6 +874,9 @@ if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'g21':
         g21_full_attention()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'g22':
+        g22_sinkhorn_loss()
+        sys.exit(0)
     g1_coarse()
     g9_metrics()
     g5_solver()
@@ -854,3 +898,4 @@ if __name__ == '__main__':
     g18_masked_training_coarse()
     g20_matcher_offdefault(ref_model()[0])
     g21_full_attention()
+    g22_sinkhorn_loss()

@@ -1,7 +1,11 @@
 """The optimal-transport coarse matcher (far_coarse_match_sinkhorn_f16s, T = 3 as in the loftr_ot configurations) against the dual-softmax
 K1 (far_coarse_match_f16s) on the same inputs, in one process: HIP events around the C calls (no host synchronisation inside the timed
 region), warm-up, then REPS alternating repetitions; the median of each.  Shapes: 32 pairs at 60 x 80 (the bench) and 16 pairs at
-68 x 90 (Map-free).  Prints one JSON line.  Usage: python tools/sinkhorn_time.py [--reps N] [--prefilter]"""
+68 x 90 (Map-free).  Prints one JSON line.  Usage: python tools/sinkhorn_time.py [--reps N] [--prefilter]
+--train: the training path instead -- far_sinkhorn_pos_conf_f16s + far_sinkhorn_pos_conf_bwd_f16 (forward + backward, T = 3) against
+far_coarse_pos_conf_f16s + far_coarse_pos_conf_bwd_f16 on the same features and positions, at 1 and 2 pairs of 60 x 80 with 1500
+positions per pair; forward and backward also timed apart.  --pairs N [N ...]: other batch sizes for the --train leg (32: the bench's
+batch, where the position grouping of the backward scans 48 000 positions)."""
 import argparse
 import ctypes
 import json
@@ -65,12 +69,78 @@ def shape_case(lib, Z, hw, reps, prefilter):
             'ratio': round(statistics.median(ts) / statistics.median(td), 3), 'sinkhorn_matches': m_skh, 'dual_softmax_matches': m_ds, 'reps': reps}
 
 
+def train_case(lib, Z, hw, reps, per_pair=1500):
+    L = hw[0] * hw[1]
+    g = torch.Generator(device='cuda').manual_seed(7)
+    f0 = 3.75 * torch.randn(Z, L, 256, device='cuda', generator=g)
+    perm = torch.randperm(L, device='cuda', generator=g)
+    f1 = f0[:, perm] + 0.1 * torch.randn(Z, L, 256, device='cuda', generator=g)
+    k = torch.randperm(L, device='cuda', generator=g)[:per_pair]
+    pb = torch.arange(Z, device='cuda').repeat_interleave(per_pair)
+    pi, pj = perm[k].repeat(Z).contiguous(), k.repeat(Z).contiguous()        # f1[:, k] = f0[:, perm[k]]
+    M = Z * per_pair
+    bs = torch.tensor(1.0, device='cuda')
+    w_pos, w0, w1 = (1e-4 * torch.randn(n, device='cuda', generator=g) for n in (M, Z * L, Z * L))
+    conf, b0, b1 = torch.empty(M, device='cuda'), torch.empty(Z, L, device='cuda'), torch.empty(Z, L, device='cuda')
+    df0, df1, dbin = torch.empty_like(f0), torch.empty_like(f1), torch.empty(1, device='cuda')
+    ws_s = torch.empty(lib.far_sinkhorn_pos_conf_workspace_bytes(Z, L, L, 256, 3), dtype=torch.uint8, device='cuda')
+    ws_d = torch.empty(lib.far_coarse_train_workspace_bytes(Z, L, L, 256), dtype=torch.uint8, device='cuda')
+    flag = ops.overflow_flag(torch.device('cuda'))
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    null = ctypes.c_void_p(0)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())
+
+    def skh_fwd():
+        return lib.far_sinkhorn_pos_conf_f16s(P(f0), P(f1), Z, L, L, 256, P(bs), 3, null, null, P(pb), P(pi), P(pj), M, P(conf), P(b0), P(b1),
+                                              P(ws_s), P(flag), st)
+
+    def skh_bwd():
+        return lib.far_sinkhorn_pos_conf_bwd_f16(P(f0), P(f1), Z, L, L, 256, P(bs), 3, null, null, P(pb), P(pi), P(pj), M, P(w_pos), P(w0),
+                                                 P(w1), P(df0), P(df1), P(dbin), P(ws_s), st)
+
+    def ds_fwd():
+        return lib.far_coarse_pos_conf_f16s(P(f0), P(f1), Z, L, L, 256, 0.1, P(pb), P(pi), P(pj), M, P(conf), P(ws_d), P(flag), st)
+
+    def ds_bwd():
+        return lib.far_coarse_pos_conf_bwd_f16(P(f0), P(f1), Z, L, L, 256, 0.1, P(pb), P(pi), P(pj), M, P(w_pos), P(df0), P(df1), P(ws_d), st)
+
+    def timed(*fns):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        rcs = [fn() for fn in fns]
+        b.record()
+        b.synchronize()
+        for rc, fn in zip(rcs, fns):
+            _lib.check(rc, fn.__name__)
+        return a.elapsed_time(b)
+
+    for _ in range(3):
+        timed(skh_fwd, skh_bwd), timed(ds_fwd, ds_bwd)
+    t = {k: [] for k in ('skh', 'skh_f', 'skh_b', 'ds', 'ds_f', 'ds_b')}
+    for _ in range(reps):
+        t['skh'].append(timed(skh_fwd, skh_bwd)); t['ds'].append(timed(ds_fwd, ds_bwd))
+        t['skh_f'].append(timed(skh_fwd)); t['skh_b'].append(timed(skh_bwd))
+        t['ds_f'].append(timed(ds_fwd)); t['ds_b'].append(timed(ds_bwd))
+    md = {k: statistics.median(v) for k, v in t.items()}
+    return {'pairs': Z, 'grid': list(hw), 'positions': M, 'sinkhorn_fwd_bwd_ms': round(md['skh'], 4), 'dual_softmax_fwd_bwd_ms': round(md['ds'], 4),
+            'ratio': round(md['skh'] / md['ds'], 3), 'sinkhorn_fwd_ms': round(md['skh_f'], 4), 'sinkhorn_bwd_ms': round(md['skh_b'], 4),
+            'dual_softmax_fwd_ms': round(md['ds_f'], 4), 'dual_softmax_bwd_ms': round(md['ds_b'], 4),
+            'bwd_ratio': round(md['skh_b'] / md['ds_b'], 3), 'reps': reps}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=25)
     ap.add_argument('--prefilter', action='store_true')
+    ap.add_argument('--train', action='store_true')
+    ap.add_argument('--pairs', type=int, nargs='+', default=[1, 2])
     a = ap.parse_args()
     lib = _lib.load()
+    if a.train:
+        res = [train_case(lib, z, (60, 80), a.reps) for z in a.pairs]
+        print(json.dumps({'tool': 'sinkhorn_time', 'leg': 'train', 'iters': 3, 'device': torch.cuda.get_device_name(),
+                          'overflow': bool(ops.overflow_flag(torch.device('cuda')).item()), 'cases': res}), flush=True)
+        return
     res = [shape_case(lib, 32, (60, 80), a.reps, a.prefilter), shape_case(lib, 16, (68, 90), a.reps, a.prefilter)]
     print(json.dumps({'tool': 'sinkhorn_time', 'iters': 3, 'prefilter': a.prefilter, 'device': torch.cuda.get_device_name(),
                       'overflow': bool(ops.overflow_flag(torch.device('cuda')).item()), 'cases': res}), flush=True)
