@@ -34,6 +34,7 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 constexpr float NEG_HUGE = -1.0e30f;
 constexpr int ROW_REF0 = -(1 << 24);     // row reference before the first tile
+constexpr float LSE_NONE = 1.0e30f;      // row statistic of a padded query row / an image without a valid key
 constexpr int P_EXP = 15;                // p is formed as 2^(x - R + 15): its fp16 lo part stays normal down to p = 2^-18 max
 
 template <int D_, int NCT_, int WAVES_>
@@ -60,6 +61,7 @@ struct Args {
     const float *q, *k, *v;
     const unsigned char *qm, *kvm;
     float* out;
+    float* lse;            // training forward: (N, H, L) log2-domain log-sum-exp of each row (NULL: inference)
     float* part_acc;       // split runs: [z][split][L][D] unnormalised accumulators,
     float* part_sum;       //             [z][split][L] row sums and
     int* part_ref;         //             [z][split][L] row references
@@ -343,6 +345,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_full_attention(Args a) {
         return;
     }
     const float den = (qok && rsum > 0.f) ? rsum : 0.f;    // 0: a padded query row / no valid key -> exact zeros
+    // the row statistic the backward recomputes p from: p = 2^(x - R + 15) / rsum = 2^(x - lse2); a row without softmax gets +1e30 (p = 0)
+    if (a.lse && h == 0 && irow < a.L) a.lse[(size_t)z * a.L + irow] = den > 0.f ? (float)(R - P_EXP) + log2f(rsum) : LSE_NONE;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int rr = mfma32_row(r, h);
@@ -378,6 +382,7 @@ __global__ __launch_bounds__(256) void k_combine(Args a, int D) {
     }
     const bool qok = !a.qm || a.qm[(size_t)n * a.L + i];
     a.out[((size_t)n * a.L + i) * (a.H * D) + hh * D + d] = (qok && den > 0.f) ? num / den * a.out_mul : 0.f;
+    if (a.lse && d == 0) a.lse[z * a.L + i] = (qok && den > 0.f) ? (float)(R - P_EXP) + log2f(den) : LSE_NONE;
 }
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -407,29 +412,8 @@ inline Plan plan(int L, int S, int H) {
     return p;
 }
 
-}  // namespace
-
-extern "C" {
-
-// Bytes of workspace far_full_attention_f16s needs for these sizes (0 when the key axis is not split; no GPU involved).
-size_t far_full_attention_workspace_bytes(int N, int L, int S, int H, int D) {
-    if (N <= 0 || L <= 0 || S <= 0 || H <= 0 || (D != 16 && D != 32)) return 0;
-    const Plan p = plan(L, S, H);
-    if (p.nsplit <= 1) return 0;
-    const size_t rows = (size_t)N * H * p.nsplit * L;
-    return align256(rows * D * 4) + 2 * align256(rows * 4);
-}
-
-// out[n, l, h, :] = sum_s softmax_s(q[n,l,h,:] . k[n,s,h,:] / sqrt(D)) v[n,s,h,:]   (LoFTR's FullAttention, inference).
-// q, out: (N, L, H D); k, v: (N, S, H D) fp32 contiguous.  D in {16, 32} (else FAR_EINVAL), H, L, S >= 1.  q_mask (N, L), kv_mask (N, S):
-// uint8 or NULL (= all ones).  A masked key is selected out (its k / v values are never used), a padded query row and every row of
-// an image without a valid key are exact zeros.  act_exp: the operands are multiplied by 2^act_exp before the fp16 split
-// (4 = the default, -24 .. 8): values up to 65504 / 2^act_exp survive it; overflow (device int or NULL) |= 1 when a q / k / v
-// value that takes part is beyond that or not finite -- `out` then holds inf / NaN.  ws: far_full_attention_workspace_bytes bytes
-// (may be NULL when that is 0).
-int far_full_attention_f16s(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D,
-                            const unsigned char* q_mask, const unsigned char* kv_mask, int act_exp, float* out, void* ws,
-                            int* overflow, hipStream_t stream) {
+int launch_forward(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D, const unsigned char* q_mask,
+                   const unsigned char* kv_mask, int act_exp, float* out, float* lse, void* ws, int* overflow, hipStream_t stream) {
     far_clear_errors();
     if (N == 0) return FAR_OK;
     if (!q || !k || !v || !out || N < 0 || L <= 0 || S <= 0 || H <= 0 || (D != 16 && D != 32) || act_exp < -24 || act_exp > 8)
@@ -438,7 +422,7 @@ int far_full_attention_f16s(const float* q, const float* k, const float* v, int 
     const long blocks = (long)N * H * p.nI * p.nsplit;
     if (blocks > 0x7fffffffL || (long)N * H > 0x7fffffffL) return FAR_EINVAL;
     Args a;
-    a.q = q; a.k = k; a.v = v; a.qm = q_mask; a.kvm = kv_mask; a.out = out; a.overflow = overflow;
+    a.q = q; a.k = k; a.v = v; a.qm = q_mask; a.kvm = kv_mask; a.out = out; a.lse = lse; a.overflow = overflow;
     a.N = N; a.L = L; a.S = S; a.H = H; a.nI = p.nI; a.nsplit = p.nsplit; a.tps = p.tps;
     a.pre = ldexpf(1.0f, act_exp);
     a.c1 = ldexpf(1.44269504088896341f / sqrtf((float)D), -2 * act_exp);       // scores -> log2 domain
@@ -465,6 +449,43 @@ int far_full_attention_f16s(const float* q, const float* k, const float* v, int 
         hipLaunchKernelGGL(k_combine, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a, D);
     }
     return far_check_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+// Bytes of workspace far_full_attention_f16s needs for these sizes (0 when the key axis is not split; no GPU involved).
+size_t far_full_attention_workspace_bytes(int N, int L, int S, int H, int D) {
+    if (N <= 0 || L <= 0 || S <= 0 || H <= 0 || (D != 16 && D != 32)) return 0;
+    const Plan p = plan(L, S, H);
+    if (p.nsplit <= 1) return 0;
+    const size_t rows = (size_t)N * H * p.nsplit * L;
+    return align256(rows * D * 4) + 2 * align256(rows * 4);
+}
+
+// out[n, l, h, :] = sum_s softmax_s(q[n,l,h,:] . k[n,s,h,:] / sqrt(D)) v[n,s,h,:]   (LoFTR's FullAttention, inference).
+// q, out: (N, L, H D); k, v: (N, S, H D) fp32 contiguous.  D in {16, 32} (else FAR_EINVAL), H, L, S >= 1.  q_mask (N, L), kv_mask (N, S):
+// uint8 or NULL (= all ones).  A masked key is selected out (its k / v values are never used), a padded query row and every row of
+// an image without a valid key are exact zeros.  act_exp: the operands are multiplied by 2^act_exp before the fp16 split
+// (4 = the default, -24 .. 8): values up to 65504 / 2^act_exp survive it; overflow (device int or NULL) |= 1 when a q / k / v
+// value that takes part is beyond that or not finite -- `out` then holds inf / NaN.  ws: far_full_attention_workspace_bytes bytes
+// (may be NULL when that is 0).
+int far_full_attention_f16s(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D,
+                            const unsigned char* q_mask, const unsigned char* kv_mask, int act_exp, float* out, void* ws,
+                            int* overflow, hipStream_t stream) {
+    return launch_forward(q, k, v, N, L, S, H, D, q_mask, kv_mask, act_exp, out, nullptr, ws, overflow, stream);
+}
+
+// The training forward: far_full_attention_f16s (the same launches, the same `out` bits) that also writes the row statistic the
+// backward (full_attention_bwd_f16s.hip) recomputes the probabilities from: lse (N, H, L) fp32, the log2-domain log-sum-exp of
+// row l's scaled scores -- the integer row reference plus log2 of the running sum; +1e30 for a padded query row and for every row
+// of an image without a valid key.  A split-key run writes it from k_combine.
+int far_full_attention_train_f16s(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D,
+                                  const unsigned char* q_mask, const unsigned char* kv_mask, int act_exp, float* out, float* lse,
+                                  void* ws, int* overflow, hipStream_t stream) {
+    if (N != 0 && !lse) return FAR_EINVAL;
+    return launch_forward(q, k, v, N, L, S, H, D, q_mask, kv_mask, act_exp, out, lse, ws, overflow, stream);
 }
 
 }  // extern "C"

@@ -166,6 +166,16 @@ class LoFTR(nn.Module):
             self.coarse_matching.bf16 = 'k1' in st
         return self
 
+    def set_full_attention_training(self, on=True):
+        """Gradients through the attention = 'full' layers of this model: K22's training forward and HIP backward
+        (ops.full_attention_train) instead of the NotImplementedError an unmodified model raises.  Sets full_training on every
+        'full' LoFTREncoderLayer and its FullAttention module; linear layers are untouched.  Inference is unchanged either way."""
+        from .transformer import LoFTREncoderLayer
+        for m in self.modules():
+            if isinstance(m, LoFTREncoderLayer) and m.full:
+                m.full_training = m.attention.full_training = bool(on)
+        return self
+
     # -------------------------------------------------------------------------------------------------
     # stage 1: local feature CNN on both images at once (loftr.py:56-89)
     # -------------------------------------------------------------------------------------------------

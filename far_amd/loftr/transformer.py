@@ -5,7 +5,7 @@ checkpoints load unchanged:
   LoFTREncoderLayer :12-67, LocalFeatureTransformer :69-112, get_positional_encodings :183-248,
   CrossAttention :250-303, CrossBlock :305-348, LocalFeatureTransformerRegressor :350-499
 and of mp3d_loftr/src/loftr/loftr_module/vit_layers/mlp.py:8-28 (Mlp).
-The attention cores run in libfar_hip.so: K5 (linear attention), K22 (full softmax attention, inference) and K2 (bilinear dual-softmax, never
+The attention cores run in libfar_hip.so: K5 (linear attention), K22 (full softmax attention) and K2 (bilinear dual-softmax, never
 materialising the (B, 4, 4800, 4800) score tensors), K6 (LayerNorm) and K9 / K15 (every Linear layer of the inference path).
 
 Batch semantics: the reference head is batch-size-1 only (its pairing reshape :339-341 and the gate
@@ -49,9 +49,11 @@ class LinearAttention(nn.Module):
 
 
 class FullAttention(nn.Module):
-    """Module-shaped handle on K22 (reference: linear_attention.py:55-88), inference only.  No parameters: state dicts are those of
+    """Module-shaped handle on K22 (reference: linear_attention.py:55-88).  No parameters: state dicts are those of
     the linear form.  Masks follow the kernel's convention: a masked key is selected out, a padded query row is
-    exact zeros -- the reference's masked form returns NaN rows there."""
+    exact zeros -- the reference's masked form returns NaN rows there.  Gradients are opt-in (full_training,
+    LoFTR.set_full_attention_training): K22's training forward and HIP backward (ops.full_attention_train)."""
+    full_training = False        # True: a gradient through the core runs K22's forward + backward kernels; False: it raises
 
     def __init__(self, use_dropout=False, attention_dropout=0.1, use_num_corres=False):
         super().__init__()
@@ -62,9 +64,15 @@ class FullAttention(nn.Module):
     def forward(self, queries, keys, values, q_mask=None, kv_mask=None, loftr_preds=None):
         N, L, H, D = queries.shape
         S = keys.shape[1]
-        if ag.needs_grad(queries, keys, values) or (self.training and self.use_dropout):
-            raise NotImplementedError('FullAttention: training / gradients through the softmax attention core are not built '
-                                      '(inference only)')
+        if self.training and self.use_dropout:
+            raise NotImplementedError('FullAttention: dropout inside the softmax attention core is not built')
+        if ag.needs_grad(queries, keys, values):
+            if not self.full_training:
+                raise NotImplementedError('FullAttention: training / gradients through the softmax attention core are off for this '
+                                          'module (inference only); LoFTR.set_full_attention_training() / full_training = True '
+                                          'turns the HIP backward on')
+            return ops.full_attention_train(queries.reshape(N, L, H * D), keys.reshape(N, S, H * D), values.reshape(N, S, H * D), H,
+                                            q_mask, kv_mask).view(N, L, H, D)
         out = ops.full_attention(queries.reshape(N, L, H * D).contiguous(), keys.reshape(N, S, H * D).contiguous(),
                                  values.reshape(N, S, H * D).contiguous(), H, q_mask, kv_mask)
         return out.view(N, L, H, D)
@@ -75,6 +83,7 @@ class LoFTREncoderLayer(nn.Module):
     dense_split = True           # ... of the launches that are plain Linear layers at d_model 256 (merge, mlp[0], mlp[2]): False =
                                  # plain fp16 there while the fused k|v-state / q-apply launches stay split ('mixed16')
     hip_training = True          # training on the GPU runs K9 / K5 (forward + backward kernels); False: vendor ops + autograd
+    full_training = False        # attention = 'full': gradients through K22 (forward + backward kernels) are opt-in; False: they raise
     layer_node = True            # ... as one autograd node per layer call (layer_train.py); False: one node per operator
     overlap = True               # layer node: weight gradients and the k / v projections on the library's side streams
     native_node = True           # layer node: launch sequences issued by the library (far_enc_layer_fwd / _bwd) instead of Python
@@ -87,7 +96,7 @@ class LoFTREncoderLayer(nn.Module):
         super().__init__()
         if attention not in ('linear', 'full'):
             raise NotImplementedError(f"attention={attention!r}: only 'linear' (the FAR configuration) and 'full' have kernels")
-        self.full = attention == 'full'          # softmax attention core (K22): inference only, no fused form (see forward)
+        self.full = attention == 'full'          # softmax attention core (K22): no fused form; gradients are opt-in (full_training)
         self.dim = d_model // nhead
         self.nhead = nhead
         self.q_proj = nn.Linear(d_model, d_model, bias=False)
@@ -105,18 +114,21 @@ class LoFTREncoderLayer(nn.Module):
 
     def forward(self, x, source, x_mask=None, source_mask=None, loftr_preds=None, out=None):
         bs = x.size(0)
-        if self.full and x.is_cuda and ag.needs_grad(x, source, self.norm1.weight):
+        if self.full and x.is_cuda and ag.needs_grad(x, source, self.norm1.weight) and not self.full_training:
             raise NotImplementedError("LoFTREncoderLayer(attention='full'): training / gradients through the softmax attention core "
-                                      'are not built (inference only)')
+                                      'are off for this layer (inference only); LoFTR.set_full_attention_training() / '
+                                      'full_training = True turns the HIP backward on')
         if self.full and not x.is_cuda:
             raise ops._lib.FarHipError("LoFTREncoderLayer(attention='full') needs tensors on the GPU (no CPU fallback exists)")
         if ag.needs_grad(x, source, self.norm1.weight) or not x.is_cuda:
-            if (x.is_cuda and self.hip_training and self.layer_node and x_mask is None and source_mask is None and x.numel()
+            # a 'full' layer with full_training on takes the per-operator path below (K9, K22 forward + backward, K6): the one-node
+            # layer is built around K5
+            if (not self.full and x.is_cuda and self.hip_training and self.layer_node and x_mask is None and source_mask is None and x.numel()
                     and source.numel() and self.dim in (16, 32) and x.shape[-1] % 4 == 0 and x.shape[-1] <= 512 and torch.is_grad_enabled()):
                 # the whole layer as ONE autograd node (layer_train.py): same kernels, no elementwise glue between them
                 from .layer_train import encoder_layer_train
                 return encoder_layer_train(self, x, source)
-            if x.is_cuda and self.hip_training:
+            if x.is_cuda and (self.hip_training or self.full):
                 # training on the GPU: the five Linear layers on K9 (forward and dgrad) and K16 (wgrad), the attention core on
                 # K5 forward + backward, both LayerNorms (the second with the residual add) on K6 forward + backward
                 pk = self.__dict__.setdefault('_packs', ops.PackCache())

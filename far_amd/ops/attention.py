@@ -26,14 +26,8 @@ def linear_attention(q, k, v, nhead, q_mask=None, kv_mask=None, eps=1e-6):
     _lib.check(rc, 'far_linear_attention_f32')
     return out
 
-def full_attention(q, k, v, nhead, q_mask=None, kv_mask=None):
-    """K22: LoFTR's full (softmax) attention core, inference only.  q: (N, L, C), k, v: (N, S, C) raw fp32 projections (heads
-    concatenated, head dim C // nhead in {16, 32}); returns (N, L, C) = softmax_s(q . k / sqrt(D)) v per head, on split-fp16 MFMAs
-    with an online softmax (the (N, L, S, H) scores never exist).  Masks (N, L) / (N, S), optional (None = all ones): a masked key
-    is selected out (non-finite k / v there never reach an output), a padded query row and every row of an image without a valid
-    key are exact zeros.  Operands are split around the thread's activation exponent; a value beyond its range ORs
-    ops.overflow_flag (check_activation_range raises)."""
-    lib = _lib.load()
+def _full_attention_args(q, k, v, nhead, q_mask, kv_mask):
+    """The argument checks K22's front ends share -> (N, L, S, C, D, q_mask, kv_mask) with the masks as contiguous uint8 (or None)."""
     for t in (q, k, v):
         if not t.is_cuda:
             raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
@@ -46,9 +40,20 @@ def full_attention(q, k, v, nhead, q_mask=None, kv_mask=None):
     D = C // nhead
     as_u8 = lambda m, n: None if m is None else m.reshape(N, n).to(torch.uint8).contiguous()
     q_mask, kv_mask = as_u8(q_mask, L), as_u8(kv_mask, S)
-    out = torch.empty(N, L, C, dtype=torch.float32, device=q.device)
     if D not in (16, 32):
         raise _lib.FarHipError(f'full_attention: head dim {D} has no kernel (16 and 32 do)')
+    return N, L, S, C, D, q_mask, kv_mask
+
+def full_attention(q, k, v, nhead, q_mask=None, kv_mask=None):
+    """K22: LoFTR's full (softmax) attention core, inference (full_attention_train is the form with gradients).  q: (N, L, C), k, v: (N, S, C) raw fp32 projections (heads
+    concatenated, head dim C // nhead in {16, 32}); returns (N, L, C) = softmax_s(q . k / sqrt(D)) v per head, on split-fp16 MFMAs
+    with an online softmax (the (N, L, S, H) scores never exist).  Masks (N, L) / (N, S), optional (None = all ones): a masked key
+    is selected out (non-finite k / v there never reach an output), a padded query row and every row of an image without a valid
+    key are exact zeros.  Operands are split around the thread's activation exponent; a value beyond its range ORs
+    ops.overflow_flag (check_activation_range raises)."""
+    lib = _lib.load()
+    N, L, S, C, D, q_mask, kv_mask = _full_attention_args(q, k, v, nhead, q_mask, kv_mask)
+    out = torch.empty(N, L, C, dtype=torch.float32, device=q.device)
     if N == 0 or L == 0:
         return out
     if S == 0:
@@ -59,6 +64,64 @@ def full_attention(q, k, v, nhead, q_mask=None, kv_mask=None):
                                      _p(overflow_flag(q.device)), _stream())
     _lib.check(rc, 'far_full_attention_f16s')
     return out
+
+class _FullAttentionFn(torch.autograd.Function):
+    """K22 with its HIP backward (far_full_attention_train_f16s / far_full_attention_bwd_f16s).  Saved: q, k, v, the output, the
+    (N, H, L) row statistic and the masks -- nothing of size (L, S)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, nhead, q_mask, kv_mask):
+        lib = _lib.load()
+        qc, kc, vc = (t.detach().float().contiguous() for t in (q, k, v))
+        N, L, C = qc.shape
+        S, D = kc.shape[1], C // nhead
+        out = torch.empty(N, L, C, dtype=torch.float32, device=qc.device)
+        lse = torch.empty(N, nhead, L, dtype=torch.float32, device=qc.device)
+        act_exp = activation_exponent_value()
+        if N and L and S:
+            ws = _ws(lib.far_full_attention_workspace_bytes(N, L, S, nhead, D), qc.device)
+            rc = lib.far_full_attention_train_f16s(_p(qc, torch.float32), _p(kc, torch.float32), _p(vc, torch.float32), N, L, S, nhead, D,
+                                                   _p(q_mask, torch.uint8), _p(kv_mask, torch.uint8), act_exp, _p(out), _p(lse), _p(ws),
+                                                   _p(overflow_flag(qc.device)), _stream())
+            _lib.check(rc, 'far_full_attention_train_f16s')
+        else:
+            out.zero_()                 # S = 0: no key, exact zeros (as full_attention)
+        none = torch.empty(0)
+        ctx.save_for_backward(qc, kc, vc, out, lse, q_mask if q_mask is not None else none, kv_mask if kv_mask is not None else none)
+        ctx.nhead, ctx.act_exp, ctx.has = nhead, act_exp, (q_mask is not None, kv_mask is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        qc, kc, vc, out, lse, qm, km = ctx.saved_tensors
+        dq, dk, dv = full_attention_bwd(qc, kc, vc, out, lse, g, ctx.nhead, qm if ctx.has[0] else None, km if ctx.has[1] else None,
+                                        act_exp=ctx.act_exp)
+        return dq, dk, dv, None, None, None
+
+def full_attention_bwd(qc, kc, vc, out, lse, g, nhead, q_mask=None, kv_mask=None, act_exp=None):
+    """K22 backward: (dq, dk, dv) for the output gradient g, from q, k, v (fp32 contiguous), the output and the (N, H, L) row
+    statistic of the training forward (same masks, same activation exponent).  No key (S = 0): zeros."""
+    lib = _lib.load()
+    N, L, C = qc.shape
+    S, D = kc.shape[1], C // nhead
+    g = g.float().contiguous()
+    dq, dk, dv = torch.empty_like(qc), torch.empty_like(kc), torch.empty_like(vc)
+    if not (N and L and S):
+        return dq.zero_(), dk.zero_(), dv.zero_()
+    ws = _ws(lib.far_full_attention_bwd_workspace_bytes(N, L, S, nhead, D), qc.device)
+    rc = lib.far_full_attention_bwd_f16s(_p(qc, torch.float32), _p(kc, torch.float32), _p(vc, torch.float32), _p(out, torch.float32),
+                                         _p(lse, torch.float32), _p(g, torch.float32), N, L, S, nhead, D, _p(q_mask, torch.uint8),
+                                         _p(kv_mask, torch.uint8), activation_exponent_value() if act_exp is None else act_exp,
+                                         _p(dq), _p(dk), _p(dv), _p(ws), _p(overflow_flag(qc.device)), _stream())
+    _lib.check(rc, 'far_full_attention_bwd_f16s')
+    return dq, dk, dv
+
+def full_attention_train(q, k, v, nhead, q_mask=None, kv_mask=None):
+    """K22 with gradients: the arguments, checks, edge cases and output bits of full_attention; (dq, dk, dv) come from the HIP
+    backward (recomputed score tiles, nothing of size (L, S) is saved or allocated).  Mask convention for gradients: dk = dv = 0
+    at a masked key, dq = 0 at a padded query row (the incoming gradient there is ignored), all zero for an image without a valid key."""
+    _, _, _, _, _, q_mask, kv_mask = _full_attention_args(q, k, v, nhead, q_mask, kv_mask)
+    return _FullAttentionFn.apply(q, k, v, nhead, q_mask, kv_mask)
 
 class _LinearAttentionFn(torch.autograd.Function):
     """K5 with its HIP backward (far_linear_attention_f32 / far_linear_attention_bwd_f32)."""

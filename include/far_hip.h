@@ -30,7 +30,7 @@ typedef struct ihipStream_t* far_stream_t; /* == hipStream_t */
 
 /* ABI version of this header; bumped when a signature changes (2: activation exponent / overflow flag of K9, K13, K14; 3: the
  * far_wino_* / far_conv3x3_wino_f32 entry points, 16 tuning keys; 4: far_upsample2x_bwd_f32, far_fine_scatter_det_f32, far_bn_train_*, far_adamw_*; 5: far_linear_kv_f16s, far_linear_q_apply_f16s,
- * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup).  far_amd/_lib.py refuses a library whose version differs. */
+ * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way).  far_amd/_lib.py refuses a library whose version differs. */
 int far_abi_version(void);
 /* Id of the sources the library was built from: sha256/16 over far_amd/csrc/* and the compiler flags (far_amd/build.py
  * source_id()).  far_amd/_lib.py refuses a library whose id differs from the sources it sits next to. */
@@ -298,6 +298,26 @@ size_t far_full_attention_workspace_bytes(int N, int L, int S, int H, int D);
 int far_full_attention_f16s(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D,
                             const uint8_t* q_mask, const uint8_t* kv_mask, int act_exp, float* out, void* ws,
                             int* overflow, far_stream_t stream);
+
+/* K22 under autograd (full_attention_f16s.hip, full_attention_bwd_f16s.hip).
+ * far_full_attention_train_f16s: far_full_attention_f16s -- the same launches, the same `out` bits, the same workspace -- that also
+ * writes lse [N][H][L] fp32: the log2-domain log-sum-exp of row l's scaled scores (+1e30 for a padded query row and for every row of
+ * an image without a valid key), from which the backward recomputes the probabilities.
+ * far_full_attention_bwd_f16s: dq [N][L][H*D], dk, dv [N][S][H*D] for g = dL/dout, from recomputed score tiles -- no (L, S)-sized
+ * tensor exists, no float atomics, an image's gradient bits do not depend on the batch it is computed in.  out, lse: what the
+ * training forward wrote for the same q, k, v, masks and act_exp.  The score recompute and dp = g . v^T run on split-fp16 operands
+ * (fp32-grade), the three output contractions on plain fp16 operands; g and ds are scaled by powers of two taken from per-image
+ * max-abs reductions on the device (no host synchronisation), so any upstream gradient scale is fine.  Masks: dk = dv = exact 0 at
+ * a masked key (its k / v values are never read), dq = exact 0 at a padded query row (g there may hold anything), all three exact 0
+ * for an image without a valid key.  overflow |= 1 when a q / k / v / g value that takes part is beyond 65504 / 2^act_exp (q, k, v)
+ * or not finite.  ws: far_full_attention_bwd_workspace_bytes(N, L, S, H, D) bytes (> 0 for every valid size; the query needs no GPU). */
+int far_full_attention_train_f16s(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D,
+                                  const uint8_t* q_mask, const uint8_t* kv_mask, int act_exp, float* out, float* lse, void* ws,
+                                  int* overflow, far_stream_t stream);
+size_t far_full_attention_bwd_workspace_bytes(int N, int L, int S, int H, int D);
+int far_full_attention_bwd_f16s(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* g,
+                                int N, int L, int S, int H, int D, const uint8_t* q_mask, const uint8_t* kv_mask, int act_exp,
+                                float* dq, float* dk, float* dv, void* ws, int* overflow, far_stream_t stream);
 
 /* K5 backward (training path): gradients of far_linear_attention_f32 w.r.t. the raw projections q, k, v given
  * g = dL/dout -- what autograd derives from linear_attention.py:31-50 in the reference.  Token-parallel kernels with the

@@ -7,7 +7,11 @@ synchronisation inside the timed region), warm-up, then REPS repetitions; the me
   * N = 4, L = S = 4800 against the materialising fp32 torch composition of linear_attention.py:74-86 on the same GPU (the one hard
     condition: the kernel is faster);
   * far_amd.pipeline.test_step with coarse.attention = 'full' against 'linear' at the bench shape (32 pairs of 480 x 640).
-Prints one JSON line.  Usage: python tools/full_attention_time.py [--reps N] [--no-step]"""
+  * --train: forward + backward of ops.full_attention_train (K22's training forward, then the backward kernels of
+    full_attention_bwd_f16s.hip) at the coarse shape (N = 4 and 64) and at the fine-window shape, the backward / forward ratio, and at
+    N = 4 fp32 torch autograd of the materialising composition on the same GPU (the hard condition of the training path: forward +
+    backward of the kernels is faster).  Only these legs run.
+Prints one JSON line.  Usage: python tools/full_attention_time.py [--reps N] [--no-step] [--train]"""
 import argparse
 import json
 import os
@@ -66,6 +70,33 @@ def against_torch(reps):
             'kernel_is_faster': tk < tt}
 
 
+def train_case(N, L, S, H, D, reps, seed=3, torch_leg=False):
+    """Forward alone, forward + backward and (their difference) the backward of ops.full_attention_train; torch_leg: fp32 autograd
+    of the materialising composition next to it."""
+    g = torch.Generator(device='cuda').manual_seed(seed)
+    q, k, v, go = (torch.randn(N, n, H * D, device='cuda', generator=g) for n in (L, S, S, L))
+    q.requires_grad_(); k.requires_grad_(); v.requires_grad_()
+
+    def fwd_bwd():
+        torch.autograd.grad(ops.full_attention_train(q, k, v, H), (q, k, v), go)
+    tf = timed(lambda: ops.full_attention_train(q, k, v, H), reps)[0]
+    tfb = timed(fwd_bwd, reps)[0]
+    mfma = (3 * 4.0 + (3 + 3 + 1) * 2.0 + (3 + 3 + 2) * 2.0) * L * S * H * D * N / MFMA_RATE * 1e3   # forward; dq kernel; dk/dv kernel
+    out = {'N': N, 'L': L, 'S': S, 'H': H, 'D': D, 'forward_ms': round(tf, 4), 'forward_backward_ms': round(tfb, 4),
+           'backward_ms': round(tfb - tf, 4), 'backward_over_forward': round((tfb - tf) / tf, 2), 'mfma_floor_ms': round(mfma, 4),
+           'fraction_of_mfma_floor': round(mfma / tfb, 3), 'reps': reps}
+    if torch_leg:
+        def composition():
+            Q, K, V = (t.view(N, n, H, D) for t, n in ((q, L), (k, S), (v, S)))
+            QK = torch.einsum('nlhd,nshd->nlsh', Q, K)
+            A = torch.softmax(QK / D ** .5, dim=2)
+            out = torch.einsum('nlsh,nshd->nlhd', A, V).reshape(N, L, H * D)
+            torch.autograd.grad(out, (q, k, v), go)
+        tt = timed(composition, max(reps // 4, 5), warm=2)[0]
+        out.update(torch_fp32_autograd_ms=round(tt, 4), torch_over_kernel=round(tt / tfb, 2), kernel_is_faster=tfb < tt)
+    return out
+
+
 def step_times(reps):
     from far_amd import synth
     from far_amd.config import far_eval_config
@@ -94,7 +125,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=20)
     ap.add_argument('--no-step', action='store_true')
+    ap.add_argument('--train', action='store_true')
     a = ap.parse_args()
+    if a.train:
+        res = {'tool': 'full_attention_time --train', 'device': torch.cuda.get_device_name(),
+               'coarse_n4': train_case(4, 4800, 4800, 8, 32, a.reps, torch_leg=True), 'coarse_n64': train_case(64, 4800, 4800, 8, 32, a.reps),
+               'fine_windows': train_case(16384, 25, 25, 8, 16, a.reps)}
+        res['overflow'] = bool(ops.overflow_flag(torch.device('cuda')).item())
+        print(json.dumps(res), flush=True)
+        return
     res = {'tool': 'full_attention_time', 'device': torch.cuda.get_device_name(),
            'coarse': kernel_case(64, 4800, 4800, 8, 32, a.reps), 'mapfree_c5': kernel_case(32, 6120, 6120, 8, 32, a.reps),
            'batch1': kernel_case(2, 4800, 4800, 8, 32, a.reps), 'fine_windows': kernel_case(16384, 25, 25, 8, 16, a.reps),
