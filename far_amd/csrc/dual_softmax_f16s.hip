@@ -367,8 +367,9 @@ static float k1_c1(float temperature) {
 }
 
 // operand planes + row statistics + dense column statistics, exactly as far_coarse_match_f16s prepares them
-int far_k1_stats_launch(const float* f0, const float* f1, int Z, int L, int S, float temperature, void* ws, int* overflow,
-                        hipStream_t stream) {
+// mask0 (Z, L) / mask1 (Z, S): optional padded masks (masked pairs count with the fill value, as far_coarse_match_f16s)
+int far_k1_stats_launch_masked(const float* f0, const float* f1, int Z, int L, int S, float temperature, const uint8_t* mask0,
+                               const uint8_t* mask1, void* ws, int* overflow, hipStream_t stream) {
     const Ws16 w = carve16(ws, Z, L, S);
     const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
     const float c1 = k1_c1(temperature), fill2 = -1e9f * 1.44269504088896341f;
@@ -378,12 +379,24 @@ int far_k1_stats_launch(const float* f0, const float* f1, int Z, int L, int S, f
     const size_t smem_s = 2 * TILE_PLANE + KT * sizeof(float);
     FAR_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)k1_rowstats<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_s));
     hipLaunchKernelGGL(k1_rowstats<false>, dim3((Lp / 128) * Z), dim3(256), smem_s, stream, w.ah, w.al, w.bh, w.bl, Z, L, S, Lp, Sp,
-                       c1, fill2, (const uint8_t*)nullptr, (const uint8_t*)nullptr, w.k.rowstat, (float*)nullptr, (float*)nullptr,
+                       c1, fill2, mask0, mask1, w.k.rowstat, (float*)nullptr, (float*)nullptr,
                        (float*)nullptr, (const float*)nullptr, (int*)nullptr, (uint2*)nullptr);
     hipLaunchKernelGGL(k1_rowstats<false>, dim3((Sp / 128) * Z), dim3(256), smem_s, stream, w.bh, w.bl, w.ah, w.al, Z, S, L, Sp, Lp,
-                       c1, fill2, (const uint8_t*)nullptr, (const uint8_t*)nullptr, w.colstat2, w.cmax, w.cinv, (float*)nullptr,
+                       c1, fill2, mask1, mask0, w.colstat2, w.cmax, w.cinv, (float*)nullptr,
                        (const float*)nullptr, (int*)nullptr, (uint2*)nullptr);
     return far_check_launch();
+}
+
+int far_k1_stats_launch(const float* f0, const float* f1, int Z, int L, int S, float temperature, void* ws, int* overflow,
+                        hipStream_t stream) {
+    return far_k1_stats_launch_masked(f0, f1, Z, L, S, temperature, nullptr, nullptr, ws, overflow, stream);
+}
+
+// dual_softmax_dense_f16s.hip: both planes of both maps and the (max, sum) statistics of both axes
+void far_k1_fwd_planes(void* ws, int Z, int L, int S, const _Float16** ah, const _Float16** al, const _Float16** bh,
+                       const _Float16** bl, const float2** rowstat, const float2** colstat) {
+    const Ws16 w = carve16(ws, Z, L, S);
+    *ah = w.ah; *al = w.al; *bh = w.bh; *bl = w.bl; *rowstat = w.k.rowstat; *colstat = w.colstat2;
 }
 
 void far_k1_fwd_views(void* ws, int Z, int L, int S, const _Float16** ah, const _Float16** bh, const float2** rowstat,

@@ -90,7 +90,15 @@ class CoarseMatching(nn.Module):
             'mkpts0_c': out['mkpts0_c'], 'mkpts1_c': out['mkpts1_c'], 'mconf': mconf,
             'match_counts': out['counts'],   # per-pair M (host), reused by the batched solver
         })
-        if 'spv_b_ids' in data and not self.materialize_conf and feat_c0.shape[-1] == 256 and 'mask0' not in data:
+        data.pop('conf_dense', None)
+        if ('spv_b_ids' in data and not self.materialize_conf and feat_c0.shape[-1] == 256
+                and not self.config.get('sparse_spvs', True)):
+            # validation of a dense-supervision configuration: the loss module evaluates ops.coarse_dense_focal_loss on this handle
+            # (forward kernels only under no_grad), masks included; no conf_matrix
+            data['conf_dense'] = {'feat_c0': feat_c0.detach(), 'feat_c1': feat_c1.detach(), 'temperature': self.temperature,
+                                  'mask0': as_u8(mask_c0), 'mask1': as_u8(mask_c1)}
+            data.pop('conf_pos', None)
+        elif 'spv_b_ids' in data and not self.materialize_conf and feat_c0.shape[-1] == 256 and 'mask0' not in data:
             # validation (lightning_loftr.py:266-267: _trainval_inference with the matcher in eval mode, then the loss):
             # the coarse loss reads conf_matrix at the ground-truth positions only (loftr_loss.py:86-91), so those are
             # evaluated instead of the dense matrix -- the forward half of the training kernels, no graph
@@ -205,11 +213,30 @@ class CoarseMatching(nn.Module):
     # the dense matrix is NOT built: K1's fused kernels select the predicted matches (no grad, as in the reference
     # where get_coarse_match runs under no_grad) and ops.coarse_pos_conf gives the differentiable confidences at
     # spv_b/i/j_ids with a HIP backward (data['conf_pos']; data['conf_matrix'] is None).  far_amd.losses mirrors the
-    # loss on them.  Padded masks take the dense autograd composition of far_amd/train_glue.py; `materialize_conf`, CPU tensors or a
+    # loss on them.  Dense supervision (sparse_spvs off) has kernels of its own: the first branch of _forward_train.  Padded masks take the dense autograd composition of far_amd/train_glue.py; `materialize_conf`, CPU tensors or a
     # feature width other than 256 need the test-side helper (far_amd/_vendor.py) -- explicitly, for drop-in use of the reference's
     # own dense loss.
     # ------------------------------------------------------------------------------------------------------
     def _forward_train(self, feat_c0, feat_c1, data, mask_c0=None, mask_c1=None):
+        data.pop('conf_dense', None)
+        if (not self.config.get('sparse_spvs', True) and feat_c0.is_cuda and feat_c0.shape[-1] == 256 and not self.materialize_conf
+                and 'spv_b_ids' in data):
+            # dense supervision (sparse_spvs = False: the loftr_ds_dense configurations; loftr_loss.py:121-127 reads EVERY entry of
+            # conf_matrix).  The matrix is still not built: the fused matcher selects the predicted matches under no_grad (masks
+            # passed down), and the loss module gets a handle on the two in-graph feature maps -- it evaluates
+            # ops.coarse_dense_focal_loss (dual_softmax_dense_f16s.hip) with its own alpha / gamma / weights.
+            as_u8 = lambda m: None if m is None else m.to(torch.uint8).contiguous()
+            m0, m1 = as_u8(mask_c0), as_u8(mask_c1)
+            with torch.no_grad():
+                out = ops.coarse_match(feat_c0.detach().float().contiguous(), feat_c1.detach().float().contiguous(),
+                                       self.temperature, self.thr, self.border_rm, data['hw0_c'], data['hw1_c'],
+                                       data['hw0_i'][0] / data['hw0_c'][0], m0, m1, self._valid_hw(data), variant=self.variant)
+                picked = self._sample_train(out['b_ids'], out['i_ids'], out['j_ids'], out['mconf'], data, feat_c0.shape[0])
+            data.update({'conf_matrix': None,
+                         'conf_dense': {'feat_c0': feat_c0, 'feat_c1': feat_c1, 'temperature': self.temperature, 'mask0': m0, 'mask1': m1}})
+            data.pop('conf_pos', None)
+            data.update(**picked)
+            return
         # padded-mask batches (coarse_matching.py:28-43, 110-117, 199-204: images of different sizes padded to one grid) take the
         # dense differentiable form: the sparse training kernels of K1 (far_coarse_pos_conf_*) carry no masks
         sparse = (feat_c0.is_cuda and feat_c0.shape[-1] == 256 and not self.materialize_conf and 'spv_b_ids' in data

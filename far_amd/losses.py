@@ -12,6 +12,11 @@ built; with a dense data['conf_matrix'] (CPU / drop-in use) the same formula ind
 LoFTRLoss (fine L2-with-std, 6D pose: loftr_loss.py:132-183, 247-276) are small torch expressions on per-match tensors,
 restated below so that LoFTRLoss.forward (:294-356) has a counterpart with the same data-dict contract.  Pinned by
 golden G15 (tools/make_goldens.py runs the reference's LoFTRLoss on the same tensors).
+
+Dense supervision (sparse_spvs = False with the dual-softmax matcher, the loftr_ds_dense configurations; :121-127) reads EVERY entry
+of conf_matrix.  coarse_focal_loss_dense evaluates it without the matrix on the GPU training path (ops.coarse_dense_focal_loss on
+the handle data['conf_dense']) and in torch on a dense data['conf_matrix'] otherwise; golden G23 pins the torch form, value and
+gradient, to the reference's compute_coarse_loss.
 """
 import torch
 
@@ -118,6 +123,56 @@ def coarse_focal_loss_sinkhorn(data, alpha=FOCAL_ALPHA, gamma=FOCAL_GAMMA, pos_w
     return term_pos + neg_weight * loss_neg.mean()                                             # :116
 
 
+def coarse_focal_loss_dense_torch(conf, ids, no_gt, alpha=FOCAL_ALPHA, gamma=FOCAL_GAMMA, pos_weight=POS_WEIGHT, neg_weight=NEG_WEIGHT,
+                                  weight=None):
+    """loftr_loss.py:56-75, :87-89, :121-127 (dense supervision, focal) on a dense conf (N, L, S): the positives are the entries
+    ids = (b, i, j), the negatives every other entry; weight: the (N, L, S) loss weight of padded batches or None.  no_gt (:65-70): the
+    positive term is the dummy entry (0, 0, 0) with weight 0, and in the weighted case that entry leaves the negative term too."""
+    pos = torch.zeros(conf.shape, dtype=torch.bool, device=conf.device)
+    if no_gt:
+        pos_weight = 0.                                                                        # :70
+        if weight is not None:
+            weight = weight.clone()
+            weight[0, 0, 0] = 0.                                                               # :68-69
+        neg = ~pos                                                                             # conf_gt == 0: every entry
+        pos = pos.clone()
+        pos[0, 0, 0] = True                                                                    # :67
+    else:
+        pos[ids] = True
+        neg = ~pos
+    q = torch.clamp(conf, 1e-6, 1 - 1e-6)                                                      # :87
+    loss_pos = -alpha * torch.pow(1 - q[pos], gamma) * q[pos].log()                            # :122
+    loss_neg = -alpha * torch.pow(q[neg], gamma) * (1 - q[neg]).log()                          # :123
+    if weight is not None:                                                                     # :124-126
+        loss_pos = loss_pos * weight[pos]
+        loss_neg = loss_neg * weight[neg]
+    return pos_weight * loss_pos.mean() + neg_weight * loss_neg.mean()                         # :127
+
+
+def coarse_focal_loss_dense(data, alpha=FOCAL_ALPHA, gamma=FOCAL_GAMMA, pos_weight=POS_WEIGHT, neg_weight=NEG_WEIGHT):
+    """The coarse loss of the *_dense configurations (sparse_spvs = False, dual_softmax, focal).  GPU training / validation path:
+    data['conf_dense'] (CoarseMatching: the two coarse feature maps, the temperature, the masks) -> ops.coarse_dense_focal_loss, one
+    scalar with a HIP backward and no L x S tensor.  Otherwise a dense data['conf_matrix'] is evaluated in torch, the positives given
+    as spv ids or as conf_matrix_gt, the weight from data['mask0'] / ['mask1'] (compute_c_weight, :190-196)."""
+    h = data.get('conf_dense')
+    if h is not None:
+        from . import ops
+        return ops.coarse_dense_focal_loss(h['feat_c0'], h['feat_c1'], data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids'],
+                                           h['temperature'], alpha, gamma, pos_weight, neg_weight, h['mask0'], h['mask1'],
+                                           no_gt=has_no_ground_truth(data))
+    conf = data['conf_matrix']
+    if 'spv_b_ids' in data:
+        ids = data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids']
+        no_gt = has_no_ground_truth(data)
+    else:
+        ids = torch.where(data['conf_matrix_gt'] == 1)
+        no_gt = ids[0].numel() == 0
+    weight = None
+    if 'mask0' in data:
+        weight = (data['mask0'].flatten(-2)[..., None] * data['mask1'].flatten(-2)[:, None]).to(conf.dtype)
+    return coarse_focal_loss_dense_torch(conf, ids, no_gt, alpha, gamma, pos_weight, neg_weight, weight)
+
+
 def fine_loss_l2_std(expec_f, expec_f_gt, correct_thr=1.0, training=True):
     """loftr_loss.py:151-183 (fine_type 'l2_with_std').  expec_f (M, 3) <x, y, std>, expec_f_gt (M, 2).  Returns None in
     eval mode when no coarse match is correct (:171-172)."""
@@ -158,7 +213,8 @@ def rt_loss(expec_rt, T_0to1, regress_rt=True, l1=True):
 
 class LoFTRLoss(torch.nn.Module):
     """Counterpart of src/losses/loftr_loss.py:LoFTRLoss for the FAR training configurations (dual_softmax, focal coarse
-    loss, sparse supervision; l2_with_std fine loss; 6D pose loss).  Same constructor argument (the lower-cased config
+    loss, sparse supervision; l2_with_std fine loss; 6D pose loss), the Sinkhorn matcher's sparse loss and the dense supervision of
+    the dual-softmax matcher (sparse_spvs = False: coarse_focal_loss_dense).  Same constructor argument (the lower-cased config
     with ['loftr']['loss'], ['loftr']['match_coarse'], ...) and the same effect: forward(data) writes data['loss'] and
     data['loss_scalars'].  On the GPU training path the coarse term reads data['conf_pos'] (K1's sparse HIP kernels);
     with a dense data['conf_matrix'] it gathers the same positions from it (given as spv ids or as conf_matrix_gt)."""
@@ -168,10 +224,13 @@ class LoFTRLoss(torch.nn.Module):
         self.config = config
         lc = self.loss_config = config['loftr']['loss']
         mc = config['loftr']['match_coarse']
-        if mc['match_type'] not in ('dual_softmax', 'sinkhorn') or lc['coarse_type'] != 'focal' or not mc.get('sparse_spvs', True):
+        self.sparse_spvs = bool(mc.get('sparse_spvs', True))
+        if (mc['match_type'] not in ('dual_softmax', 'sinkhorn') or lc['coarse_type'] != 'focal'
+                or (not self.sparse_spvs and mc['match_type'] != 'dual_softmax')):
             raise NotImplementedError('far_amd.losses.LoFTRLoss covers dual_softmax / sinkhorn + focal + sparse supervision '
-                                      '(the FAR training scripts, the loftr_ot configurations); cross-entropy / dense supervision '
-                                      'are not built')
+                                      '(the FAR training scripts, the loftr_ot configurations) and dual_softmax + focal + dense '
+                                      'supervision (the loftr_ds_dense configurations); cross-entropy and dense supervision of the '
+                                      'Sinkhorn matcher are not built')
         self.match_type = mc['match_type']
         self.correct_thr = lc['fine_correct_thr']
         self.c_pos_w = lc['pos_weight']
@@ -191,12 +250,16 @@ class LoFTRLoss(torch.nn.Module):
         cfg = self.config
         lc = self.loss_config
         ref = next((data[k] for k in ('conf_pos', 'conf_matrix', 'conf_matrix_with_bin') if data.get(k) is not None), None)
+        if ref is None and data.get('conf_dense') is not None:
+            ref = data['conf_dense']['feat_c0']
         dev = ref.device if ref is not None else data['expec_rt'].device
         loss = torch.zeros(1, device=dev)                                                      # :303
         scalars = {}
         if cfg['loftr'].get('from_saved_preds') is None and not cfg.get('use_correspondence_transformer', False):
             d = data
-            if self.match_type == 'sinkhorn':
+            if not self.sparse_spvs:
+                loss_c = coarse_focal_loss_dense(data, lc['focal_alpha'], lc['focal_gamma'], self.c_pos_w, self.c_neg_w)
+            elif self.match_type == 'sinkhorn':
                 loss_c = coarse_focal_loss_sinkhorn(data, lc['focal_alpha'], lc['focal_gamma'], self.c_pos_w, self.c_neg_w)
             else:
                 if data.get('conf_pos') is None and 'spv_b_ids' not in data:                   # dense drop-in use: positions from conf_matrix_gt

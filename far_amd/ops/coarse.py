@@ -191,6 +191,66 @@ class _CoarsePosConf(torch.autograd.Function):
         _lib.check(rc, 'far_coarse_pos_conf_bwd_f16')
         return df0, df1, None, None, None, None
 
+class _CoarseDenseFocal(torch.autograd.Function):
+    """The dense-supervision focal loss of the dual-softmax matcher (loftr_loss.py:121-127) as ONE scalar, differentiable w.r.t. both
+    coarse feature maps, without conf_matrix or any other L x S tensor (far_coarse_dense_focal_f16s / far_coarse_dense_focal_bwd_f16)."""
+
+    @staticmethod
+    def forward(ctx, f0, f1, pb, pi, pj, mask0, mask1, temperature, alpha, gamma, pos_weight, neg_weight, no_gt):
+        lib = _lib.load()
+        Z, L, C = f0.shape
+        S = f1.shape[1]
+        dev = f0.device
+        f0c, f1c = f0.detach().float().contiguous(), f1.detach().float().contiguous()
+        pb, pi, pj = (t.to(torch.int64).contiguous() for t in (pb, pi, pj))
+        m0 = None if mask0 is None else mask0.reshape(Z, L).to(torch.uint8).contiguous()
+        m1 = None if mask1 is None else mask1.reshape(Z, S).to(torch.uint8).contiguous()
+        M = int(pb.numel())
+        ws = _ws(lib.far_coarse_dense_focal_workspace_bytes(Z, L, S, C, M), dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        ctx.args = (Z, L, S, C, float(temperature))
+        ctx.focal = (float(alpha), float(gamma), float(pos_weight), float(neg_weight), int(bool(no_gt)))
+        rc = lib.far_coarse_dense_focal_f16s(_p(f0c, torch.float32), _p(f1c, torch.float32), *ctx.args, _p(m0), _p(m1), _p(pb), _p(pi),
+                                             _p(pj), M, *ctx.focal, _p(loss), _p(ws), _p(overflow_flag(dev)), _stream())
+        _lib.check(rc, 'far_coarse_dense_focal_f16s')
+        ctx.save_for_backward(f0c, f1c, pb, pi, pj, ws)
+        ctx.masks = (m0, m1)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        f0c, f1c, pb, pi, pj, ws = ctx.saved_tensors
+        m0, m1 = ctx.masks
+        gup = g.detach().float().reshape(1).contiguous()                      # stays on the device: no host read
+        df0, df1 = torch.empty_like(f0c), torch.empty_like(f1c)
+        rc = lib.far_coarse_dense_focal_bwd_f16(_p(f0c), _p(f1c), *ctx.args, _p(m0), _p(m1), _p(pb), _p(pi), _p(pj), int(pb.numel()),
+                                                *ctx.focal, _p(gup, torch.float32), int(DENSE_FOCAL_SPLIT_G), _p(df0), _p(df1), _p(ws),
+                                                _stream())
+        _lib.check(rc, 'far_coarse_dense_focal_bwd_f16')
+        return (df0, df1) + (None,) * 11
+
+
+# The gradient contraction's G = 2 W - u R - v C as an fp16 hi + lo pair (True) or as one fp16 (False); measured errors of both forms:
+# profiles/dense_spvs_parity.txt
+DENSE_FOCAL_SPLIT_G = True
+
+
+def coarse_dense_focal_loss(f0, f1, pb, pi, pj, temperature, alpha, gamma, pos_weight, neg_weight, mask0=None, mask1=None, no_gt=False):
+    """K1, training with dense coarse supervision (sparse_spvs = False, dual_softmax, focal: loftr_loss.py:56-75, :121-127): the loss
+    over EVERY entry of the (Z, L, S) confidence matrix as a 0-dim fp32 tensor with a HIP backward to both feature maps; positives =
+    the labels (pb, pi, pj), negatives = every other entry; mask0 (Z, L) / mask1 (Z, S): the loss weight mask0 x mask1 and the masked
+    softmaxes of padded batches.  no_gt: not one ground-truth match (the labels are ignored).  Nothing of size L x S is allocated.
+    C must be 256."""
+    if not (f0.is_cuda and f1.is_cuda):
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if f0.shape[-1] != 256:
+        raise NotImplementedError('the dense coarse supervision has kernels for C = 256 only')
+    if f0.shape[0] == 0 or f0.shape[1] == 0 or f1.shape[1] == 0:
+        return (f0.sum() + f1.sum()) * 0.0
+    return _CoarseDenseFocal.apply(f0, f1, pb, pi, pj, mask0, mask1, temperature, alpha, gamma, pos_weight, neg_weight, no_gt)
+
+
 SINKHORN_MAX_ITERS = 48          # far_sinkhorn_pos_conf_*: the 2T terms of a column tile are staged in LDS
 
 

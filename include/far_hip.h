@@ -193,6 +193,27 @@ int far_sinkhorn_pos_conf_bwd_f16(const float* f0, const float* f1, int Z, int L
                                   int M, const float* w_pos, const float* w_bin0, const float* w_bin1, float* df0, float* df1,
                                   float* dbin, void* ws, far_stream_t stream);
 
+/* K1 on the training path with DENSE coarse supervision (dual_softmax_dense_f16s.hip): match_type 'dual_softmax', coarse_type
+ * 'focal', sparse_spvs = False (src/losses/loftr_loss.py:56-75, :87-89, :121-127; the loftr_ds_dense configurations).
+ *   q = clamp(p, 1e-6, 1 - 1e-6);  loss = pos_weight mean_pos(w (-alpha (1 - q)^gamma log q)) + neg_weight mean_neg(w (-alpha q^gamma log(1 - q)))
+ * over EVERY entry of conf_matrix (positives: the M labels pb / pi / pj, negatives: the other Z L S - M entries; w = mask0 x mask1),
+ * without conf_matrix, conf_matrix_gt or any other tensor of size L S.  no_gt != 0 (not one ground-truth match, :65-70): the labels
+ * are ignored, the positive term vanishes and, with masks, entry (0, 0, 0) leaves the negative term.  C must be 256.
+ * ws: far_coarse_dense_focal_workspace_bytes(Z, L, S, C, M) bytes (0: unsupported shape), kept untouched between the forward and
+ * the backward call.  forward: loss_out = one device float.  No float atomics: the same bits at every launch. */
+size_t far_coarse_dense_focal_workspace_bytes(int Z, int L, int S, int C, int M);
+int far_coarse_dense_focal_f16s(const float* f0, const float* f1, int Z, int L, int S, int C, float temperature,
+                                const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj,
+                                int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, float* loss_out,
+                                void* ws, int* overflow, far_stream_t stream);
+/* backward: the same arguments as the forward call; gup = one device float (dL/dloss).  df0 (Z, L, C), df1 (Z, S, C) are overwritten;
+ * rows of masked cells get exactly 0.  Score tiles recomputed on the split-fp16 operands; G = 2 W - u R - v C enters the gradient
+ * contraction as one fp16 (split_g = 0) or as an fp16 hi + lo pair (split_g = 1); the other map's operand is plain fp16. */
+int far_coarse_dense_focal_bwd_f16(const float* f0, const float* f1, int Z, int L, int S, int C, float temperature,
+                                   const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj,
+                                   int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, const float* gup,
+                                   int split_g, float* df0, float* df1, void* ws, far_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * K2  EMM head: bilinear dual-softmax attention  F = v~^T (softmax_row(s) * softmax_col(s)) v~
  * replaces src/loftr/loftr_module/transformer.py:275-292 (CrossAttention.forward), one call per direction

@@ -2,8 +2,8 @@
 
 Container-only: needs /root/reference and tools/ref_shim.py.  The fixtures are data (seeds, small inputs,
 expected outputs); no reference source is copied.  Weights come from far_amd.synth (seeded), inputs from
-seeds recorded in each file.  Run:  python tools/make_goldens.py  (all of g1 ... g18, g20, g21 and g22; `python tools/make_goldens.py g20`
-for one; g19 comes from tools/make_golden_vit.py).  g21 = the full softmax attention core, layer and stack (attention = 'full').  g20 = LoFTR.forward off the default launch sequence of far_amd (unequal image
+seeds recorded in each file.  Run:  python tools/make_goldens.py  (all of g1 ... g18 and g20 ... g23; `python tools/make_goldens.py g20`
+for one; g19 comes from tools/make_golden_vit.py).  g23 = the dense-supervision focal loss (sparse_spvs = False) with its gradient.  g21 = the full softmax attention core, layer and stack (attention = 'full').  g20 = LoFTR.forward off the default launch sequence of far_amd (unequal image
 sizes, padded masks, scales), with the fp32 run's deviation from the float64 oracle stored next to it.
 """
 import importlib.util
@@ -828,6 +828,46 @@ def g22_sinkhorn_loss():
     print('g22:', {k: float(v) for k, v in out.items()})
 
 
+def g23_dense_focal():
+    """LoFTRLoss.compute_coarse_loss (loftr_loss.py:56-75, :87-89, :121-127) of the reference with sparse_spvs = False (dual_softmax,
+    focal): a small dense conf_matrix (2, 48, 48) with entries beyond both clamps and confident negatives, with and without the
+    padded-mask weight, with and without ground truth (:65-70).  Each case: the loss and its gradient w.r.t. conf.  Data only."""
+    from src.losses.loftr_loss import LoFTRLoss
+    from far_amd.config import far_train_config
+    cfg = far_train_config()
+    cfg['loftr']['match_coarse']['sparse_spvs'] = False
+    cfg['loftr']['loss']['neg_weight'] = 0.7
+    lf = LoFTRLoss(cfg).train()
+    rng = np.random.default_rng(123)
+    N, hw = 2, (6, 8)
+    L = S = hw[0] * hw[1]
+    conf = (rng.random((N, L, S)) ** 6).astype(np.float32)
+    conf[rng.random(conf.shape) < 0.05] = 0.0
+    conf[rng.random(conf.shape) < 0.01] = 1.0
+    conf[rng.random(conf.shape) < 0.01] = np.float32(1.0 - 3e-5)           # confident negatives inside the clamp
+    gt = np.zeros((N, L, S), np.float32)
+    for n in range(N):
+        k = 15 + 4 * n
+        gt[n, rng.permutation(L)[:k], rng.permutation(S)[:k]] = 1.0
+    for n in range(N):                                   # confident true matches, as a trained matcher gives
+        ii, jj = np.nonzero(gt[n])
+        conf[n, ii[::2], jj[::2]] = (0.5 + 0.5 * rng.random(len(ii[::2]))).astype(np.float32)
+    m0 = np.zeros((N,) + hw, bool)
+    m1 = np.zeros((N,) + hw, bool)
+    m0[0, :5, :8] = True; m0[1, :6, :6] = True
+    m1[0, :6, :5] = True; m1[1, :4, :7] = True
+    weight = (m0.reshape(N, L)[..., None] * m1.reshape(N, S)[:, None]).astype(np.float32)
+    out = {}
+    for tag, g, w in (('plain', gt, None), ('weight', gt, weight), ('nogt', np.zeros_like(gt), None), ('nogt_weight', np.zeros_like(gt), weight)):
+        c = torch.from_numpy(conf.copy()).requires_grad_(True)
+        loss = lf.compute_coarse_loss(c, torch.from_numpy(g.copy()), None if w is None else torch.from_numpy(w.copy()))
+        loss.backward()
+        out['loss_' + tag] = loss.detach().numpy()
+        out['grad_' + tag] = c.grad.numpy()
+    save('g23_dense_focal', seed=123, neg_weight=np.float32(0.7), conf=conf, gt=gt.astype(np.int8), mask0=m0, mask1=m1, **out)
+    print('g23:', {k: float(v) for k, v in out.items() if k.startswith('loss')})
+
+
 def g8_manifest(m):
     man = {k: list(v.shape) for k, v in m.state_dict().items()}
     with open(os.path.join(OUT, 'g8_state_dict_manifest.json'), 'w') as f:
@@ -877,6 +917,9 @@ if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'g22':
         g22_sinkhorn_loss()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'g23':
+        g23_dense_focal()
+        sys.exit(0)
     g1_coarse()
     g9_metrics()
     g5_solver()
@@ -899,3 +942,4 @@ if __name__ == '__main__':
     g20_matcher_offdefault(ref_model()[0])
     g21_full_attention()
     g22_sinkhorn_loss()
+    g23_dense_focal()
