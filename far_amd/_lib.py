@@ -55,6 +55,11 @@ SIGNATURES = {
                                           c_p, c_p, c_p, c_p]),
     'far_coarse_dense_focal_bwd_f16': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_f, c_i,
                                              c_p, c_i, c_p, c_p, c_p, c_p]),
+    'far_sinkhorn_dense_focal_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    'far_sinkhorn_dense_focal_f16s': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_f,
+                                            c_i, c_p, c_p, c_p, c_p]),
+    'far_sinkhorn_dense_focal_bwd_f16': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_f, c_f, c_f, c_f,
+                                               c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     'far_emm_pv_f32': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     'far_fine_gather_f32': (c_i, [c_p, c_l, c_l, c_l, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),
     'far_fine_scatter_f32': (c_i, [c_p, c_l, c_l, c_l, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p]),

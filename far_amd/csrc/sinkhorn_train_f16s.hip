@@ -19,6 +19,8 @@
 //                   tile.  One kernel, launched twice with the roles of the maps swapped
 //     k_skt_group   the sparse part of G: positions that share a row are found by a wave-wide scan and handled by ONE wave in position
 //                   order (their sums for ubar / vbar; the first four of a row as slots for k_skt_bwd; the rest as row additions) -- no float atomics anywhere, every launch computes the same bits every time
+// Dense supervision (sparse_spvs = False: far_sinkhorn_dense_focal_f16s / far_sinkhorn_dense_focal_bwd_f16) shares all of the above:
+// its kernels (k_skd_*) and entry points are at the end of this file, its backward is skt_backward with k_skt_bwd<.., DENSE>.
 // Potentials, adjoint vectors and the 2T-term contraction are fp32; the weights are scaled by a power of two so that the dense part
 // sits in the fp16 range at any gradient scale (scale_exp).  No data is handed between the workgroups of one launch.
 #include "k1_f16s.h"
@@ -38,6 +40,35 @@ constexpr int TILE_T = C * TROW;         // 20 KiB
 constexpr int STAGE = 2 * TILE_X + TILE_T;   // 52 KiB: hi and lo plane tiles + the transposed tile (+ the column terms)
 
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// ---- dense supervision (far_sinkhorn_dense_focal_*: the kernels are at the end of this file) ----
+constexpr float LN2 = 0.693147180559945309f;
+constexpr float P_LO = 1e-6f;                        // the loss reads q = clamp(p, 1e-6, 1 - 1e-6)
+constexpr float P_HI = (float)(1.0 - 1e-6);
+constexpr float DEAD = -0.5f * HUGE_F;               // a potential below this marks a padded or masked row / column
+
+struct FocalK {
+    float alpha, gamma, cneg;                        // cneg = neg_weight / (N L S - #positives)
+    double c_lo, c_hi;                               // the negative term of an entry clamped from below / from above
+};
+struct DenseK {                                      // what k_skt_bwd<.., DENSE> needs beyond the sparse kernel's arguments
+    const float *dr, *dc;                            // k_skd_side's potentials of the row side [Z][Nrp] and the column side [Z][Ncp]
+    const float* gup;                                // the upstream gradient, one device float
+    float cneg, alpha, gamma;
+};
+
+// The negative-form focal term -alpha p^gamma log(1 - p) of an entry p = 2^xe inside the clamp's range, and W = (d term / d p) p.
+// p^gamma comes from the exponent; log(1 - p) is one hardware log, except below 2^-8 where 1 - p would lose p's digits (series to
+// p^4: relative error < p^4 / 5 < 5e-11).  ONE definition for the loss pass, the labels' correction and the gradient kernel: the
+// same p gives the same bits everywhere.
+__device__ __forceinline__ float neg_w(float p, float xe, float alpha, float gamma, float& term) {
+    const float om = 1.0f - p;
+    const float ser = -p * (1.0f + p * (0.5f + p * (0.333333343f + p * 0.25f)));
+    const float l1 = p < 0.00390625f ? ser : __builtin_amdgcn_logf(om) * LN2;
+    const float qg = ex2(gamma * xe);
+    term = -alpha * qg * l1;
+    return alpha * qg * (p * __builtin_amdgcn_rcpf(om) - gamma * l1);
+}
 
 // sum over the 256 threads of a workgroup in a fixed order (butterfly per wave, the four waves in order); valid in thread 0
 __device__ __forceinline__ float block_sum(float s, float* red, int tid) {
@@ -209,12 +240,42 @@ __global__ __launch_bounds__(256) void k_skt_group(const int64_t* __restrict__ p
     }
 }
 
+// score_tile (k1_f16s.h) with the two cross terms in the other order: hi.hi + lo.hi + hi.lo in (tile, row) terms -- the order in which
+// score_tile accumulates the same entry when the maps' roles are swapped
+__device__ __forceinline__ void score_tile_x(f32x16 (&acc)[2], const unsigned char* lds, const RowFrags& rf, int l31, int h) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        f16x8 ch[2], cl[2];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+            const int row = 32 * ct + l31;
+            const int off = row * ROWB + (((2 * s + h) ^ (row & 15)) * 16);
+            ch[ct] = *reinterpret_cast<const f16x8*>(lds + off);
+            cl[ct] = *reinterpret_cast<const f16x8*>(lds + TILE_PLANE + off);
+        }
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], rf.hi[s], acc[ct], 0, 0, 0);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[ct], rf.hi[s], acc[ct], 0, 0, 0);
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], rf.lo[s], acc[ct], 0, 0, 0);
+    }
+}
+
 // One adjoint half-step over the rows of the (Nr x Nc) score matrix of (a, b):
 //   out_r   = keep out_r   - ( sum_{c < Nc} cw_c 2^(x_rc + rpot_r + cpot_c - N)     + cwbin 2^(alpha + rpot_r + cbinpot - cmarg_bin) )
 //   outbin  = keep outbin  - ( sum_{c < Nc} cw_c 2^(alpha + rbinpot + cpot_c - N)   + cwbin 2^(alpha + rbinpot + cbinpot - cmarg_bin) )
 // rpot / cpot: the potentials of the two sides at this half-step (log2 units; padded: -huge), N = log2 of a real row's / column's
 // marginal, cmarg_bin that of the column side's dustbin.  cw: the column side's adjoint vector (padded: 0).  The tile loop is
 // k_skh_stats' (sinkhorn_f16s.hip); the workgroup of row block 0 also reduces the dustbin row.
+// XORD (the dense backward): the two cross terms of a score are accumulated the other way round (score_tile_x) -- then this pass
+// meets the potentials it divides by with the very scores they were summed from (the statistics launch had the maps' roles swapped),
+// and a row whose mass sits on one entry gets p = 1 - (the rest) instead of 1 +- the rounding of a 768-term sum.
+template <bool XORD = false>
 __global__ __launch_bounds__(256, 2) void k_skt_adj(const _Float16* __restrict__ ah, const _Float16* __restrict__ al,
                                                     const _Float16* __restrict__ bh, const _Float16* __restrict__ bl,
                                                     int Z, int Nr, int Nc, int Nrp, int Ncp, float c1,
@@ -260,7 +321,8 @@ __global__ __launch_bounds__(256, 2) void k_skt_adj(const _Float16* __restrict__
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         f32x16 acc[2];
-        score_tile(acc, lds, rf, l31, h);
+        if constexpr (XORD) score_tile_x(acc, lds, rf, l31, h);
+        else score_tile(acc, lds, rf, l31, h);
         const bool special = (jt + 1) * KT > Nc || cmask != nullptr || rmask != nullptr;      // wave-uniform
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct)
@@ -382,15 +444,21 @@ __device__ __forceinline__ void dma_lin(unsigned char* lds, const unsigned char*
 // the position's own weight, a relative score error delta would stay as delta |w| next to a result of (1 - P) |w|.  The sum of
 // slots and terms is formed in fp32 and leaves as an fp16 (hi, lo) pair; the other map's tile is plain fp16.
 // NR > 0: the lane's row terms live in registers (nterm <= NR); NR = 0: they are re-read per tile (any nterm).
+// DENSE != 0 (dense supervision, far_sinkhorn_dense_focal_bwd_f16): G carries one more term per entry, the focal loss's own
+//   W_ij = wsc neg_w(p_ij),  p_ij = 2^(x_ij + dr_row + dc_col)  (dr / dc: k_skd_side's potentials; wsc = cneg gup 2^e),
+// recomputed from the tile's score with the expression and the MFMA order of the forward's loss pass (k_skd_pass), so that p has
+// the forward's bits and falls on the same side of the clamp.  DENSE = 1: the rows are f1's, 2: the rows are f0's; both forms
+// accumulate every score in both orders of its cross terms (see below).  DENSE = 0 compiles to the sparse kernel.
 // grid: Z * Nrp / 128 workgroups of 4 waves; wave = 32 rows x 256 channels of the output (128 accumulator registers)
-template <int NR>
+template <int NR, int DENSE = 0>
 __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__ ah, const _Float16* __restrict__ al,
                                                     const _Float16* __restrict__ bh, const _Float16* __restrict__ bl,
                                                     const unsigned char* __restrict__ bt, int Z, int Nr, int Nc, int Nrp, int Ncp,
                                                     float c1, int nterm, const float* __restrict__ rw, const float* __restrict__ re,
                                                     const float* __restrict__ cw, const float* __restrict__ ce,
                                                     const int* __restrict__ slot_j, const float* __restrict__ slot_w,
-                                                    const unsigned* __restrict__ wmax_bits, float kappa, float* __restrict__ out) {
+                                                    const unsigned* __restrict__ wmax_bits, float kappa, float* __restrict__ out,
+                                                    DenseK dk) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
     int z, Ib;
@@ -399,6 +467,11 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
     RowFrags rf;
     rf.load(ah, al, (size_t)z * Nrp + irow, irow, h);
     const size_t rstride = (size_t)Z * Nrp, cstride = (size_t)Z * Ncp;
+    float drow = 0.f, wsc = 0.f;
+    if constexpr (DENSE != 0) {
+        drow = dk.dr[(size_t)z * Nrp + irow];
+        wsc = dk.cneg * dk.gup[0] * ldexpf(1.0f, scale_exp(wmax_bits + z, nterm));
+    }
     const float* const rwp = rw + (size_t)z * Nrp + irow;
     const float* const rep = re + (size_t)z * Nrp + irow;
     float rwr[NR > 0 ? NR : 1], rer[NR > 0 ? NR : 1];
@@ -426,7 +499,7 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
     for (int nt = 0; nt < 8; ++nt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
-    const int stage = STAGE + nterm * 256;                        // tile planes + [nterm][W 32 | E 32] column terms
+    const int stage = STAGE + nterm * 256 + (DENSE ? 256 : 0);    // tile planes + [nterm][W 32 | E 32] column terms (+ the dense term's potentials)
     const int ntile = Ncp / KB;
     auto request = [&](int jt, int st) {
         unsigned char* base = lds + st * stage;
@@ -438,6 +511,10 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
             const float* src = ((o & 32) ? ce : cw) + (size_t)k * cstride + (size_t)z * Ncp + jt * KB + c;
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + STAGE + (o - lane) * 4), 4, 0, 0);
         }
+        if constexpr (DENSE != 0) {
+            if (wave == 0)                                        // 32 column potentials (the upper half-wave repeats them into the pad)
+                __builtin_amdgcn_global_load_lds((gptr_t)(dk.dc + (size_t)z * Ncp + jt * KB + l31), (lptr_t)(base + STAGE + nterm * 256), 4, 0, 0);
+        }
     };
     request(0, 0);
     for (int jt = 0; jt < ntile; ++jt) {
@@ -448,9 +525,9 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
         const unsigned char* xs = lds + st * stage;
         const float* const cp = reinterpret_cast<const float*>(xs + STAGE);
         // ---- scores, transposed: D[m = column of the tile][n = this lane's row], split-fp16 as in the forward
-        f32x16 sc;
+        f32x16 sc, sx;
 #pragma unroll
-        for (int r = 0; r < 16; ++r) sc[r] = 0.f;
+        for (int r = 0; r < 16; ++r) { sc[r] = 0.f; sx[r] = 0.f; }
 #pragma unroll
         for (int s = 0; s < NS; ++s) {
             const int off = l31 * ROWB + (((2 * s + h) ^ (l31 & 15)) * 16);
@@ -459,6 +536,11 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
             sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.hi[s], sc, 0, 0, 0);
             sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sc, 0, 0, 0);
             sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sc, 0, 0, 0);
+            if constexpr (DENSE != 0) {                           // the same entry with the two cross terms the other way round
+                sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.hi[s], sx, 0, 0, 0);
+                sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sx, 0, 0, 0);
+                sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sx, 0, 0, 0);
+            }
         }
         // ---- G for this lane's row and its 16 columns  c = (r & 3) + 8 (r >> 2) + 4 h; a score that is not finite can only come from a
         // masked row or column (W = 0, E = -huge there): taken as 0 so that it stays out of the products
@@ -466,7 +548,18 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
         for (int r = 0; r < 16; ++r) {
             const float x = sc[r] * c1;
             sc[r] = fabsf(x) < HUGE_F ? x : 0.f;
+            if constexpr (DENSE != 0) {
+                const float y = sx[r] * c1;
+                sx[r] = fabsf(y) < HUGE_F ? y : 0.f;
+            }
         }
+        // Dense forms: every term meets the score its potentials were normalised with.  The column half-iterations (rows of f1, tiles
+        // of f0) summed hi.hi + f0hi.f1lo + f0lo.f1hi, the row half-iterations the cross terms the other way round; `sc` is the former
+        // when this launch's rows are f1's (DENSE = 1) and the latter when they are f0's (DENSE = 2).  A row whose mass sits on one
+        // entry has 2^(x + U - N) = 1 - (the rest) only with the score U was summed from -- and ds = G (1 - p - (1 - p) p') is the
+        // difference that remains.  Even terms and the loss's W: column order; odd terms: row order.
+        const f32x16& xcol = DENSE == 2 ? sx : sc;
+        const f32x16& xrow = DENSE == 2 ? sc : sx;
         f16x8 gp[2], gl[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {                             // eight columns at a time (registers)
@@ -481,7 +574,12 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
                     const float ww[4] = {w4.x, w4.y, w4.z, w4.w}, ee[4] = {e4.x, e4.y, e4.z, e4.w};
 #pragma unroll
                     for (int e = 0; e < 4; ++e)
-                        g[4 * q + e] = fmaf(rwk * ww[e], ex2(sc[8 * u + 4 * q + e] + (rek + ee[e])), g[4 * q + e]);
+                        if constexpr (DENSE != 0) {
+                            const float xs_ = (k & 1) ? xrow[8 * u + 4 * q + e] : xcol[8 * u + 4 * q + e];
+                            g[4 * q + e] = fmaf(rwk * ww[e], ex2(xs_ + (rek + ee[e])), g[4 * q + e]);
+                        } else {
+                            g[4 * q + e] = fmaf(rwk * ww[e], ex2(sc[8 * u + 4 * q + e] + (rek + ee[e])), g[4 * q + e]);
+                        }
                 }
             };
             if (NR > 0) {
@@ -490,6 +588,21 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
                     if (k < nterm) term(k, rwr[k], rer[k]);
             } else {
                 for (int k = 0; k < nterm; ++k) term(k, rwp[k * rstride], rep[k * rstride]);
+            }
+            if constexpr (DENSE != 0) {                           // the loss's own W at every entry inside the clamp's range
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    const float4 c4 = *reinterpret_cast<const float4*>(cp + nterm * 64 + 8 * (2 * u + q) + 4 * h);
+                    const float cc[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float xe = xcol[8 * u + 4 * q + e] + (drow + cc[e]);
+                        const float p = ex2(xe);
+                        float term;
+                        const float wv = neg_w(p, xe, dk.alpha, dk.gamma, term);
+                        g[4 * q + e] = fmaf((p >= P_LO && p <= P_HI) ? wv : 0.f, wsc, g[4 * q + e]);
+                    }
+                }
             }
 #pragma unroll
             for (int q = 0; q < KFOLD; ++q) {                     // the positions of this row that fall into this half tile
@@ -570,6 +683,283 @@ __global__ void k_skt_dbin_sum(const float* __restrict__ part, int Z, float* __r
     }
 }
 
+// =====================================================================================================================
+// Dense supervision of the optimal-transport matcher (match_type 'sinkhorn', sparse_spvs = False: the loftr_ot_dense configurations;
+// loftr_loss.py:56-75, :87-89, :121-127).  The loss reads EVERY entry of conf = P[:, :L, :S] (the dustbin row and column are not
+// supervised):
+//     q = clamp(p, 1e-6, 1 - 1e-6);  loss = c_pos sum_pos w (-alpha (1 - q)^gamma log q) + c_neg sum_neg w (-alpha q^gamma log(1 - q))
+//     c_pos = pos_weight / M,  c_neg = neg_weight / (N L S - M),  w_ij = mask0_i mask1_j
+// so G = dloss/dlogP is dense on the real block, G_ij = W_ij = (dloss/dp_ij) p_ij, and zero on the dustbins.  Nothing of L x S
+// elements exists: every entry is treated as a negative by tile passes, the M labels are corrected afterwards (negative term out,
+// positive term in), as in dual_softmax_dense_f16s.hip.
+//   forward   far_sinkhorn_dense_focal_f16s   the T statistics launches of far_sinkhorn_pos_conf_f16s (every (u^t, v^t) kept), then
+//     k_skd_side       the final potentials with padded and masked rows / columns at -huge: p_ij = 2^(x_ij + (dr_i + dc_j))
+//     k_skd_pass x2    32-column split-fp16 tile loop; a lane owns one row across all column tiles: ubar_i = sum_j c_neg W_ij, per
+//                      workgroup one float64 partial of the loss, per pair the max of |c_neg W|; the second launch swaps the maps
+//                      (vbar_j).  Both form x_ij from the three MFMAs in ONE order (that of the last column half-iteration, whose
+//                      sum normalised p), so an entry has the same bits in both launches, in k_skd_pos and in the gradient kernel:
+//                      it is inside or outside the clamp everywhere alike.
+//     k_skd_pos        the labels: p_k with the bits of the tile pass, the correction of the loss (float64) and of W
+//     k_skd_loss       partials and corrections summed in a fixed order -> one device float
+//   backward  far_sinkhorn_dense_focal_bwd_f16  k_skd_seed (ubar^T = gup ubar, vbar^T = gup vbar, dustbin seeds 0, the labels'
+//             weights gup dW_k), then skt_backward: the sparse backward's launches with k_skt_bwd<.., DENSE> and the labels as its
+//             positions.  gup is one device float: no host read.
+// No float atomics (one integer atomicMax on float bits per wave, k_skd_pass): the same bits at every launch.
+// =====================================================================================================================
+constexpr int DT = 32;                     // columns per tile of the loss pass
+constexpr int PLANE32 = DT * ROWB;         // 16 KiB: one plane of a tile
+
+__global__ void k_skd_side(const float* __restrict__ uT, const float* __restrict__ vT, const uint8_t* __restrict__ mask0,
+                           const uint8_t* __restrict__ mask1, int Z, int L, int S, int Lp, int Sp, float nrm, float* __restrict__ dr,
+                           float* __restrict__ dc) {
+    const long nl = (long)Z * Lp, total = nl + (long)Z * Sp;
+    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
+        if (t < nl) {
+            const int i = (int)(t % Lp);
+            const long z = t / Lp;
+            dr[t] = (i < L && !(mask0 && !mask0[z * L + i])) ? uT[t] : -HUGE_F;
+        } else {
+            const long q = t - nl;
+            const int j = (int)(q % Sp);
+            const long z = q / Sp;
+            dc[q] = (j < S && !(mask1 && !mask1[z * S + j])) ? vT[q] - nrm : -HUGE_F;
+        }
+    }
+}
+
+// the score of the loss passes from an accumulator entry: what is not finite can only come from a masked row or column (p = 0 there)
+__device__ __forceinline__ float skd_score(float a, float c1) {
+    const float x = a * c1;
+    return fabsf(x) < HUGE_F ? x : 0.f;
+}
+
+// SWAP: the rows are f0's (the tile holds f1): the two cross terms in the order in which the column half-iteration (rows of f1, tiles
+// of f0, score_tile) accumulated them.  roww[z][row] = cneg sum_cols W; lossp[workgroup] (unless null) = its share of the sum of the
+// negative-form terms; gmax_bits[z] (unless null) = max |cneg W|.
+// grid: Z * Nrp / 128 workgroups of 4 waves; a wave = 32 rows, its two halves take interleaved columns
+template <bool SWAP>
+__global__ __launch_bounds__(256, 2) void k_skd_pass(const _Float16* __restrict__ ah, const _Float16* __restrict__ al,
+                                                     const _Float16* __restrict__ bh, const _Float16* __restrict__ bl, int Z, int Nr, int Nc,
+                                                     int Nrp, int Ncp, float c1, const float* __restrict__ rpot,
+                                                     const float* __restrict__ cpot, float* __restrict__ roww, FocalK fk,
+                                                     unsigned* __restrict__ gmax_bits, double* __restrict__ lossp) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+    __shared__ double wsum[4];
+    constexpr int STG = 2 * PLANE32;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
+    int z, Ib;
+    tile_coords(Nrp / 128, Z, z, Ib);
+    const int irow = Ib * 128 + 32 * wave + l31;
+    RowFrags rf;
+    rf.load(ah, al, (size_t)z * Nrp + irow, irow, h);
+    const float rp = rpot[(size_t)z * Nrp + irow];
+    const bool rvalid = rp > DEAD;
+    float usum = 0.f, wmx = 0.f;
+    double lsum = 0.0;
+    int nlo = 0, nhi = 0;
+    float* const cw = reinterpret_cast<float*>(lds + 2 * STG);    // [2 stages][32 column potentials]
+    const int ntile = (Nc + DT - 1) / DT;
+    auto request = [&](int jt, int st) {
+        unsigned char* base = lds + st * STG;
+        const size_t row0 = (size_t)z * Ncp + (size_t)jt * DT;
+        dma_lin(base, reinterpret_cast<const unsigned char*>(bh + row0 * C), PLANE32, tid, wave);
+        dma_lin(base + PLANE32, reinterpret_cast<const unsigned char*>(bl + row0 * C), PLANE32, tid, wave);
+        if (tid < DT) cw[st * DT + tid] = cpot[row0 + tid];
+    };
+    request(0, 0);
+    for (int jt = 0; jt < ntile; ++jt) {
+        const int st = jt & 1;
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();                                          // tile jt landed; every read of stage st ^ 1 has returned
+        if (jt + 1 < ntile) request(jt + 1, st ^ 1);
+        const unsigned char* xs = lds + st * STG;
+        f32x16 sc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int off = l31 * ROWB + (((2 * s + h) ^ (l31 & 15)) * 16);
+            const f16x8 ch = *reinterpret_cast<const f16x8*>(xs + off);
+            const f16x8 cl = *reinterpret_cast<const f16x8*>(xs + PLANE32 + off);
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.hi[s], sc, 0, 0, 0);
+            if (SWAP) {
+                sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sc, 0, 0, 0);
+                sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sc, 0, 0, 0);
+            } else {
+                sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sc, 0, 0, 0);
+                sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sc, 0, 0, 0);
+            }
+        }
+        // ---- this lane's row and its 16 columns  c = (r & 3) + 8 (r >> 2) + 4 h
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 c4 = *reinterpret_cast<const float4*>(cw + st * DT + 8 * q + 4 * h);
+            const float cc[4] = {c4.x, c4.y, c4.z, c4.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool ok = rvalid && cc[e] > DEAD;           // a real pair with both cells unmasked
+                const float xe = skd_score(sc[4 * q + e], c1) + (rp + cc[e]);
+                const float p = ex2(xe);
+                if (p >= P_LO && p <= P_HI) {
+                    float term;
+                    const float wc = neg_w(p, xe, fk.alpha, fk.gamma, term) * fk.cneg;
+                    lsum += (double)term;
+                    usum += wc;
+                    wmx = fmaxf(wmx, fabsf(wc));
+                } else {
+                    nlo += (ok && p < P_LO) ? 1 : 0;
+                    nhi += p > P_HI ? 1 : 0;
+                }
+            }
+        }
+    }
+    usum += shfl_xor_f(usum, 32);                                 // the two half-waves hold interleaved columns of the same rows
+    if (h == 0) roww[(size_t)z * Nrp + irow] = usum;
+    if (gmax_bits) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) wmx = fmaxf(wmx, shfl_xor_f(wmx, m));
+        if (lane == 0 && wmx > 0.f && wmx < HUGE_F) atomicMax(gmax_bits + z, __float_as_uint(wmx));     // non-negative floats order as uints
+    }
+    if (lossp) {
+        double tot = lsum + fk.c_lo * (double)nlo + fk.c_hi * (double)nhi;
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) tot += __shfl_xor(tot, m, 64);
+        if (lane == 0) wsum[wave] = tot;
+        __syncthreads();
+        if (tid == 0) lossp[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+    }
+}
+
+// The labels: what replacing the negative term by the positive one changes, dl[k] in the loss and dw[k] in W.  p_k must be the very
+// value the tile passes formed at (b_k, i_k, j_k), so it is recomputed the same way (k1d_pos of dual_softmax_dense_f16s.hip): one
+// wave per 32 labels gathers their rows of the operand planes into one 32 x 32 MFMA problem (tile role: the labels' columns of f1, row
+// role: their rows of f0, the order of k_skd_pass<true>) and reads its diagonal.  A label out of range or on a masked cell is not
+// read and corrects nothing.
+__global__ __launch_bounds__(256) void k_skd_pos(const _Float16* __restrict__ ah, const _Float16* __restrict__ al,
+                                                 const _Float16* __restrict__ bh, const _Float16* __restrict__ bl, int Z, int L, int S,
+                                                 int Lp, int Sp, float c1, const int64_t* __restrict__ pb, const int64_t* __restrict__ pi,
+                                                 const int64_t* __restrict__ pj, int M, const float* __restrict__ dr,
+                                                 const float* __restrict__ dc, FocalK fk, double cpos, double* __restrict__ dl,
+                                                 float* __restrict__ dw, unsigned* __restrict__ gmax_bits) {
+    const int lane = threadIdx.x & 63, l31 = lane & 31, h = lane >> 5;
+    const int nw = gridDim.x * (blockDim.x >> 6);
+    for (int k0 = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) * 32; k0 < M; k0 += nw * 32) {      // wave-uniform
+        const int k = min(k0 + l31, M - 1);
+        const long zb = pb[k], ib = pi[k], jb = pj[k];
+        const bool inr = pos_ok(zb, ib, jb, Z, L, S);
+        const size_t z = inr ? (size_t)zb : 0, i = inr ? (size_t)ib : 0, j = inr ? (size_t)jb : 0;
+        const _Float16 *ra = ah + (z * Lp + i) * C, *rl = al + (z * Lp + i) * C, *ca = bh + (z * Sp + j) * C, *cb = bl + (z * Sp + j) * C;
+        f32x16 sc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sc[r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const int so = 8 * ((2 * s + h) ^ (int)(j & 15)), ro = 8 * ((2 * s + h) ^ (int)(i & 15));
+            const f16x8 ch = *reinterpret_cast<const f16x8*>(ca + so), cl = *reinterpret_cast<const f16x8*>(cb + so);
+            const f16x8 rh = *reinterpret_cast<const f16x8*>(ra + ro), rlo = *reinterpret_cast<const f16x8*>(rl + ro);
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rh, sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rh, sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rlo, sc, 0, 0, 0);
+        }
+        // the diagonal: this lane's column l31 against tile row mfma32_row(r, h) == l31
+        const int rd = (l31 & 3) + 4 * (l31 >> 3);
+        float dd = 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (r == rd) dd = sc[r];
+        if (h == ((l31 >> 2) & 1) && k0 + l31 < M) {
+            double t = 0.0, w = 0.0;
+            const float rp = dr[z * Lp + i], cp = dc[z * Sp + j];
+            if (inr && rp > DEAD && cp > DEAD) {
+                const float xe = skd_score(dd, c1) + (rp + cp);
+                const float p = ex2(xe);
+                const bool in = p >= P_LO && p <= P_HI;
+                float tnf = 0.f;
+                const float wnf = neg_w(p, xe, fk.alpha, fk.gamma, tnf);                  // the very numbers the tile passes added
+                const double q = fmin(fmax((double)p, 1e-6), 1.0 - 1e-6), al_ = fk.alpha, ga = fk.gamma;
+                const double lq = log(q), og = pow(1.0 - q, ga);
+                const double tn = in ? (double)tnf : (p < P_LO ? fk.c_lo : fk.c_hi);
+                const double wn = in ? (double)wnf : 0.0;
+                const double tp = -al_ * og * lq;
+                const double wp = in ? al_ * (ga * q * (og / (1.0 - q)) * lq - og) : 0.0;
+                t = cpos * tp - (double)fk.cneg * tn;
+                w = cpos * wp - (double)fk.cneg * wn;
+            }
+            dl[k0 + l31] = t;
+            dw[k0 + l31] = (float)w;
+            // |dW_k| joins the pair's largest weight: the gradient kernel's power-of-two scale then keeps every label's weight within
+            // the range of the slots (<= FOLD_MAX for T >= 1), so that it meets the tile's own W at that entry in fp32.  A label
+            // routed past the tile instead would leave -dW_k there to be multiplied by the fp16-rounded feature row while dW_k
+            // itself meets the fp32 one: where ds ~ 0 on a confidently matched row, that rounding is all that remains (measured:
+            // 1.2e-2 on dF at T = 1 with pos_weight 0.3 / neg_weight 300, where |dW_k| ~ 2 max |adjoint weight|).
+            const float aw = fabsf((float)w);
+            if (aw > 0.f && aw < HUGE_F) atomicMax(gmax_bits + z, __float_as_uint(aw));
+        }
+    }
+}
+
+// loss = cneg * sum of the workgroups' partials + sum of the labels' corrections: one workgroup, a fixed order
+__global__ __launch_bounds__(256) void k_skd_loss(const double* __restrict__ lossp, int nparts, const double* __restrict__ dl, int M,
+                                                  double cneg, float* __restrict__ loss_out) {
+    __shared__ double sh[256];
+    double a = 0.0, b = 0.0;
+    for (int t = threadIdx.x; t < nparts; t += 256) a += lossp[t];
+    for (int t = threadIdx.x; t < M; t += 256) b += dl[t];
+    sh[threadIdx.x] = cneg * a + b;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m) sh[threadIdx.x] += sh[threadIdx.x + m];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) loss_out[0] = (float)sh[0];
+}
+
+// The seeds of the adjoint recursion at t = T: ubar = gup ubar_dense, vbar = gup vbar_dense (the labels' part is added by
+// k_skt_group<0>), dustbin seeds 0 (the dustbin row and column carry no loss term); the labels' weights gup dW_k.  One workgroup per pair.
+__global__ __launch_bounds__(256) void k_skd_seed(const float* __restrict__ u, const float* __restrict__ v, const float* __restrict__ dw, int M,
+                                                  const float* __restrict__ gup, int Z, int Lp, int Sp, float* __restrict__ ubar,
+                                                  float* __restrict__ vbar, float* __restrict__ barbin, float* __restrict__ wpos) {
+    const int z = blockIdx.x, tid = threadIdx.x;
+    const float g = gup[0];
+    for (int i = tid; i < Lp; i += 256) ubar[(size_t)z * Lp + i] = g * u[(size_t)z * Lp + i];
+    for (int j = tid; j < Sp; j += 256) vbar[(size_t)z * Sp + j] = g * v[(size_t)z * Sp + j];
+    for (int k = z * 256 + tid; k < M; k += Z * 256) wpos[k] = g * dw[k];
+    if (tid == 0) { barbin[z] = 0.f; barbin[Z + z] = 0.f; }
+}
+
+// wmax[z] = max(wmax[z], |gup| gmax[z]): behind k_skt_wmax, one thread per pair
+__global__ void k_skd_wjoin(const unsigned* __restrict__ gmax_bits, const float* __restrict__ gup, int Z, unsigned* __restrict__ wmax_bits) {
+    for (int z = threadIdx.x; z < Z; z += blockDim.x) {
+        const float m = fabsf(gup[0]) * __uint_as_float(gmax_bits[z]);
+        if (m > 0.f && m < HUGE_F && __float_as_uint(m) > wmax_bits[z]) wmax_bits[z] = __float_as_uint(m);
+    }
+}
+
+// d bin_score of the dense backward, from the dustbin adjoints alone.  k_skt_dbin sums dZc over the dustbin row and column term by
+// term; with no loss term on the dustbins almost all of that cancels analytically -- the dustbin row of a row half-step sums to its
+// marginal (sum_j Pr(L, j) = 1), the dustbin column of a column half-step likewise, and ubar_L / vbar_S are themselves minus the sums
+// they meet there -- while numerically the marginals hold to ~1e-6 only, which at one iteration left 1.7e-3 of a d bin_score that is
+// 1500 times smaller than the terms.  Substituting the recursion leaves, per pair,
+//   d bin_score = vbar^0_S + sum_{t = 1 .. T} ( vbar^t_S Pc^t(L, S) + ubar^t_L Pr^t(L, S) )       (T >= 1; 0 for T = 0)
+// with Pc^t(L, S) = 2^(alpha + U^t_L + V^t_S - lnu_S), Pr^t(L, S) = 2^(alpha + U^t_L - lmu_L + V^{t-1}_S): terms of the size of the
+// result.  One thread, pairs and steps in order.
+__global__ void k_skd_dbin(const float* __restrict__ binh, const float* __restrict__ barbin, const float* __restrict__ bin_score, int Z, int T,
+                           float lmu_l, float lnu_s, float* __restrict__ dbin) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const float alpha = bin_score[0] * LOG2E;
+    float tot = 0.f;
+    for (int z = 0; z < Z; ++z) {
+        float s = T > 0 ? barbin[Z + z] : 0.f;                                            // vbar^0_S
+        for (int t = 1; t <= T; ++t) {
+            const float ubin = binh[(size_t)t * 2 * Z + z], vbin = binh[(size_t)t * 2 * Z + Z + z], vbinq = binh[(size_t)(t - 1) * 2 * Z + Z + z];
+            const float ubarL = barbin[(size_t)t * 2 * Z + z], vbarS = barbin[(size_t)t * 2 * Z + Z + z];
+            s += fmaf(vbarS, ex2(alpha + ubin + vbin - lnu_s), ubarL * ex2(alpha + ubin - lmu_l + vbinq));
+        }
+        tot += s;
+    }
+    dbin[0] = tot;
+}
+
 struct WsT {
     _Float16 *ah, *al, *bh, *bl;
     float *uh, *vh, *binh;           // [(T+1)][Z][Lp], [(T+1)][Z][Sp], [(T+1)][2][Z]: every (u^t, v^t) and the dustbin potentials
@@ -608,6 +998,54 @@ inline WsT carve_t(void* ws, int Z, int L, int S, int T) {
 
 inline bool dims_ok(int Z, int L, int S, int Cc, int T) {
     return Z > 0 && L > 0 && S > 0 && Cc == C && T >= 0 && T <= MAX_ITERS && (long)Z * ((L > S ? L : S) + 128) <= 0x7ff00000L;
+}
+
+struct WsD {                         // behind WsT in the workspace of the dense entry points
+    float *pr, *pc;                  // [Z][Lp], [Z][Sp]: k_skd_side
+    float *u, *v;                    // [Z][Lp], [Z][Sp]: ubar / vbar of the dense part (unscaled)
+    double *lossp, *dl;              // [Z Lp / 128], [max(M, 1)]
+    float *dw, *wpos;                // [max(M, 1)] x2: the labels' correction of W, and gup times it
+    unsigned* gmax;                  // [Z]
+    size_t bytes;
+};
+inline WsD carve_d(void* ws, size_t o, int Z, int L, int S, int M) {
+    WsD w;
+    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const size_t Mc = M > 0 ? M : 1;
+    unsigned char* p = (unsigned char*)ws;
+    auto take = [&](size_t n) { unsigned char* r = p ? p + o : nullptr; o += align256(n); return r; };
+    w.pr = (float*)take((size_t)Z * Lp * 4); w.pc = (float*)take((size_t)Z * Sp * 4);
+    w.u = (float*)take((size_t)Z * Lp * 4); w.v = (float*)take((size_t)Z * Sp * 4);
+    w.lossp = (double*)take((size_t)Z * (Lp / 128) * 8);
+    w.dl = (double*)take(Mc * 8);
+    w.dw = (float*)take(Mc * 4); w.wpos = (float*)take(Mc * 4);
+    w.gmax = (unsigned*)take((size_t)Z * 4);
+    w.bytes = o;
+    return w;
+}
+
+struct DenseRun {
+    const float *pr, *pc, *gup;
+    const unsigned* gmax;
+    float cneg, alpha, gamma;
+};
+int skt_backward(const WsT& w, const float* f0, const float* f1, int Z, int L, int S, const float* bin_score, int T,
+                 const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj, int M,
+                 const float* w_pos, const float* w_bin0, const float* w_bin1, float* df0, float* df1, float* dbin, const DenseRun* dn,
+                 hipStream_t stream);
+
+// the normalisers of a call (loftr_loss.py:63-70: without ground truth the positive term has weight 0 and every entry is a negative;
+// the labels handed over then only leave the negative term -- the caller passes the dummy entry (0, 0, 0) for a weighted batch)
+inline void make_plan(int Z, int L, int S, int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, FocalK& fk,
+                      double& cpos) {
+    const long npos = no_gt ? 0 : M;
+    const double nneg = (double)Z * (double)L * (double)S - (double)npos;
+    fk.alpha = alpha;
+    fk.gamma = gamma;
+    fk.cneg = nneg > 0 ? (float)((double)neg_weight / nneg) : 0.f;
+    fk.c_lo = -(double)alpha * pow(1e-6, (double)gamma) * log1p(-1e-6);
+    fk.c_hi = -(double)alpha * pow(1.0 - 1e-6, (double)gamma) * log(1e-6);
+    cpos = npos > 0 ? (double)pos_weight / (double)npos : 0.0;
 }
 
 }  // namespace
@@ -653,41 +1091,61 @@ int far_sinkhorn_pos_conf_bwd_f16(const float* f0, const float* f1, int Z, int L
         return FAR_EINVAL;
     const WsT w = carve_t(ws, Z, L, S, iters);
     const int T = iters, Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const size_t nu = (size_t)Z * Lp, nv = (size_t)Z * Sp;
+    // ---- ubar^T = rowsum(G), vbar^T = colsum(G) without the positions
+    hipLaunchKernelGGL(k_skt_seed, dim3(Z), dim3(256), 0, stream, w_bin0, w_bin1, Z, L, S, Lp, Sp, w.ubar + T * nu, w.vbar + T * nv,
+                       w.barbin + (size_t)T * 2 * Z);
+    return skt_backward(w, f0, f1, Z, L, S, bin_score, T, mask0, mask1, pb, pi, pj, M, w_pos, w_bin0, w_bin1, df0, df1, dbin, nullptr, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+// Everything of the backward behind the seeds ubar^T / vbar^T (the caller has written them without the positions' part): the
+// positions' sums, the 2T adjoint half-steps, ds on the matrix core, the positions' own part, d bin_score (dense: k_skd_dbin).  dn: the dense term of
+// far_sinkhorn_dense_focal_bwd_f16 (null: the sparse backward, launch for launch what it was).
+int skt_backward(const WsT& w, const float* f0, const float* f1, int Z, int L, int S, const float* bin_score, int T,
+                 const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj, int M,
+                 const float* w_pos, const float* w_bin0, const float* w_bin1, float* df0, float* df1, float* dbin, const DenseRun* dn,
+                 hipStream_t stream) {
+    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
     const float c1 = (float)(1.4426950408889634 / ((double)C * PRESCALE * PRESCALE));
     const double n2 = -std::log2((double)L + (double)S);
     const float nrm = (float)n2, lmu_l = (float)(std::log2((double)S) + n2), lnu_s = (float)(std::log2((double)L) + n2);
     const size_t nu = (size_t)Z * Lp, nv = (size_t)Z * Sp;
     auto gridp = [](long n) { long g = (n + 255) / 256; return (unsigned)(g < 16384 ? (g > 0 ? g : 1) : 16384); };
     const unsigned gpos = (unsigned)std::min((M + 3) / 4, 2048);
-    // ---- ubar^T = rowsum(G), vbar^T = colsum(G)
-    hipLaunchKernelGGL(k_skt_seed, dim3(Z), dim3(256), 0, stream, w_bin0, w_bin1, Z, L, S, Lp, Sp, w.ubar + T * nu, w.vbar + T * nv,
-                       w.barbin + (size_t)T * 2 * Z);
     if (M > 0)
         hipLaunchKernelGGL(k_skt_group<0>, dim3(gpos, 2), dim3(256), 0, stream, pb, pi, pj, w_pos, M, Z, L, S, Lp, Sp, mask0, mask1,
                            w.ubar + T * nu, w.vbar + T * nv, (const float*)nullptr, (const float*)nullptr, 0.f, (float*)nullptr,
                            (float*)nullptr, (const unsigned*)nullptr, 0, 0, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr);
     // ---- the adjoint half-steps, t = T .. 1
     const size_t smem_a = 2 * TILE_PLANE + (2 * KT + 8) * sizeof(float);
-    FAR_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)k_skt_adj, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_a));
+    FAR_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)k_skt_adj<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_a);
+                        hipFuncSetAttribute((const void*)k_skt_adj<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_a));
+    auto* adj = dn ? k_skt_adj<true> : k_skt_adj<false>;
     for (int t = T; t >= 1; --t) {
         const float* bt = w.binh + (size_t)t * 2 * Z;            // (U_L, V_S) at t
         const float* bq = w.binh + (size_t)(t - 1) * 2 * Z;
         float* ab = w.barbin + (size_t)t * 2 * Z;                // (ubar_L, vbar_S) at t
         float* aq = w.barbin + (size_t)(t - 1) * 2 * Z;
         // column half-step: rows = the L side, weights vbar^t, potentials (u^t, v^t)
-        hipLaunchKernelGGL(k_skt_adj, dim3((Lp / 128) * Z), dim3(256), smem_a, stream, w.ah, w.al, w.bh, w.bl, Z, L, S, Lp, Sp, c1,
+        hipLaunchKernelGGL(adj, dim3((Lp / 128) * Z), dim3(256), smem_a, stream, w.ah, w.al, w.bh, w.bl, Z, L, S, Lp, Sp, c1,
                            mask0, mask1, (const float*)(w.uh + t * nu), bt, (const float*)(w.vh + t * nv), bt + Z,
                            (const float*)(w.vbar + t * nv), (const float*)(ab + Z), bin_score, nrm, lnu_s, t == T ? 1 : 0,
                            w.ubar + t * nu, ab);
         // row half-step: rows = the S side, weights ubar^t, potentials (v^{t-1}, u^t)
-        hipLaunchKernelGGL(k_skt_adj, dim3((Sp / 128) * Z), dim3(256), smem_a, stream, w.bh, w.bl, w.ah, w.al, Z, S, L, Sp, Lp, c1,
+        hipLaunchKernelGGL(adj, dim3((Sp / 128) * Z), dim3(256), smem_a, stream, w.bh, w.bl, w.ah, w.al, Z, S, L, Sp, Lp, c1,
                            mask1, mask0, (const float*)(w.vh + (t - 1) * nv), bq + Z, (const float*)(w.uh + t * nu), bt,
                            (const float*)(w.ubar + t * nu), (const float*)ab, bin_score, nrm, lmu_l, 0, w.vbar + (t - 1) * nv, aq + Z);
     }
     // ---- dense part of ds on the matrix core
-    if (T > 0) {
+    if (T > 0 || dn) {
         hipMemsetAsync(w.wmax, 0, (size_t)Z * 4, stream);
         hipLaunchKernelGGL(k_skt_wmax, dim3(8, Z), dim3(256), 0, stream, (const float*)w.ubar, (const float*)w.vbar, Z, Lp, Sp, T, w.wmax);
+        if (dn)       // the dense term's largest weight joins the pair's maximum: it shares the fp16 tile with the 2T terms
+            hipLaunchKernelGGL(k_skd_wjoin, dim3(1), dim3(256), 0, stream, dn->gmax, dn->gup, Z, w.wmax);
         hipLaunchKernelGGL(k_skt_pack, dim3(gridp((long)2 * T * (nu + nv))), dim3(256), 0, stream, (const float*)w.uh, (const float*)w.vh,
                            (const float*)w.ubar, (const float*)w.vbar, Z, L, S, Lp, Sp, T, nrm, mask0, mask1, (const unsigned*)w.wmax,
                            w.wl, w.el, w.wsd, w.es);
@@ -701,22 +1159,34 @@ int far_sinkhorn_pos_conf_bwd_f16(const float* f0, const float* f1, int Z, int L
         hipLaunchKernelGGL(k_skt_prep_t, dim3(gridp((long)Z * (Lp / KB) * C * 4)), dim3(256), 0, stream, f0, Z, L, Lp, mask0, w.at);
         hipLaunchKernelGGL(k_skt_prep_t, dim3(gridp((long)Z * (Sp / KB) * C * 4)), dim3(256), 0, stream, f1, Z, S, Sp, mask1, w.bt);
         const int nterm = 2 * T;
-        const size_t smem = 2 * (size_t)(STAGE + nterm * 256);
+        const size_t smem = 2 * (size_t)(STAGE + nterm * 256 + (dn ? 256 : 0));
         const size_t smem_max = 2 * (size_t)(STAGE + 2 * MAX_ITERS * 256);
+        const size_t smem_maxd = smem_max + 2 * 256;
         FAR_ONCE_PER_DEVICE(
             hipFuncSetAttribute((const void*)k_skt_bwd<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max);
             hipFuncSetAttribute((const void*)k_skt_bwd<12>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max);
-            hipFuncSetAttribute((const void*)k_skt_bwd<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max));
-        auto* kern = nterm <= 6 ? k_skt_bwd<6> : nterm <= 12 ? k_skt_bwd<12> : k_skt_bwd<0>;
+            hipFuncSetAttribute((const void*)k_skt_bwd<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max);
+            hipFuncSetAttribute((const void*)k_skt_bwd<6, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_maxd);
+            hipFuncSetAttribute((const void*)k_skt_bwd<6, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_maxd);
+            hipFuncSetAttribute((const void*)k_skt_bwd<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_maxd);
+            hipFuncSetAttribute((const void*)k_skt_bwd<0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_maxd));
+        // the dense forms: rows of f0 meet the scores in the order <.., 2>, rows of f1 in the order <.., 1> (k_skd_pass's two launches)
+        auto* kern0 = !dn ? (nterm <= 6 ? k_skt_bwd<6> : nterm <= 12 ? k_skt_bwd<12> : k_skt_bwd<0>) : (nterm <= 6 ? k_skt_bwd<6, 2> : k_skt_bwd<0, 2>);
+        auto* kern1 = !dn ? kern0 : (nterm <= 6 ? k_skt_bwd<6, 1> : k_skt_bwd<0, 1>);
+        DenseK d0{}, d1{};
+        if (dn) {
+            d0 = DenseK{dn->pr, dn->pc, dn->gup, dn->cneg, dn->alpha, dn->gamma};
+            d1 = DenseK{dn->pc, dn->pr, dn->gup, dn->cneg, dn->alpha, dn->gamma};
+        }
         const float kappa = (float)(1.0 / (double)C);
-        hipLaunchKernelGGL(kern, dim3((Lp / 128) * Z), dim3(256), smem, stream, (const _Float16*)w.ah, (const _Float16*)w.al,
+        hipLaunchKernelGGL(kern0, dim3((Lp / 128) * Z), dim3(256), smem, stream, (const _Float16*)w.ah, (const _Float16*)w.al,
                            (const _Float16*)w.bh, (const _Float16*)w.bl, (const unsigned char*)w.bt, Z, L, S, Lp, Sp, c1, nterm,
                            (const float*)w.wl, (const float*)w.el, (const float*)w.wsd, (const float*)w.es, (const int*)w.sj0,
-                           (const float*)w.sw0, (const unsigned*)w.wmax, kappa, df0);
-        hipLaunchKernelGGL(kern, dim3((Sp / 128) * Z), dim3(256), smem, stream, (const _Float16*)w.bh, (const _Float16*)w.bl,
+                           (const float*)w.sw0, (const unsigned*)w.wmax, kappa, df0, d0);
+        hipLaunchKernelGGL(kern1, dim3((Sp / 128) * Z), dim3(256), smem, stream, (const _Float16*)w.bh, (const _Float16*)w.bl,
                            (const _Float16*)w.ah, (const _Float16*)w.al, (const unsigned char*)w.at, Z, S, L, Sp, Lp, c1, nterm,
                            (const float*)w.wsd, (const float*)w.es, (const float*)w.wl, (const float*)w.el, (const int*)w.sj1,
-                           (const float*)w.sw1, (const unsigned*)w.wmax, kappa, df1);
+                           (const float*)w.sw1, (const unsigned*)w.wmax, kappa, df1, d1);
     } else {
         hipMemsetAsync(df0, 0, (size_t)Z * L * C * 4, stream);
         hipMemsetAsync(df1, 0, (size_t)Z * S * C * 4, stream);
@@ -725,12 +1195,87 @@ int far_sinkhorn_pos_conf_bwd_f16(const float* f0, const float* f1, int Z, int L
     if (M > 0)
         hipLaunchKernelGGL(k_skt_group<2>, dim3(gpos, 2), dim3(256), 0, stream, pb, pi, pj, w_pos, M, Z, L, S, Lp, Sp, mask0, mask1,
                            (float*)nullptr, (float*)nullptr, f0, f1, (float)(1.0 / (double)C), df0, df1, (const unsigned*)w.wmax,
-                           T > 0 ? KFOLD : 0, T, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr);
+                           (T > 0 || dn) ? KFOLD : 0, T, (int*)nullptr, (float*)nullptr, (int*)nullptr, (float*)nullptr);
+    if (dn) {
+        hipLaunchKernelGGL(k_skd_dbin, dim3(1), dim3(64), 0, stream, (const float*)w.binh, (const float*)w.barbin, bin_score, Z, T, lmu_l, lnu_s, dbin);
+        return far_check_launch();
+    }
     hipLaunchKernelGGL(k_skt_dbin, dim3(Z), dim3(256), 0, stream, w_bin0, w_bin1, (const float*)w.uh, (const float*)w.vh,
                        (const float*)w.binh, (const float*)w.ubar, (const float*)w.vbar, (const float*)w.barbin, bin_score, Z, L, S, Lp, Sp,
                        T, nrm, lmu_l, lnu_s, w.part);
     hipLaunchKernelGGL(k_skt_dbin_sum, dim3(1), dim3(64), 0, stream, (const float*)w.part, Z, dbin);
     return far_check_launch();
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t far_sinkhorn_dense_focal_workspace_bytes(int Z, int L, int S, int Cc, int iters, int M) {
+    if (!dims_ok(Z, L, S, Cc, iters) || M < 0) return 0;
+    return carve_d(nullptr, carve_t(nullptr, Z, L, S, iters).bytes, Z, L, S, M).bytes;
+}
+
+int far_sinkhorn_dense_focal_f16s(const float* f0, const float* f1, int Z, int L, int S, int Cc, const float* bin_score, int iters,
+                                  const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj,
+                                  int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, float* loss_out,
+                                  void* ws, int* overflow, hipStream_t stream) {
+    far_clear_errors();
+    if (!f0 || !f1 || !bin_score || !ws || !loss_out || !dims_ok(Z, L, S, Cc, iters) || M < 0 || (M > 0 && (!pb || !pi || !pj)))
+        return FAR_EINVAL;
+    const WsT w = carve_t(ws, Z, L, S, iters);
+    const WsD d = carve_d(ws, w.bytes, Z, L, S, M);
+    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    FocalK fk;
+    double cpos;
+    make_plan(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt, fk, cpos);
+    const int rc = far_skh_history_launch(f0, f1, Z, L, S, bin_score, iters, mask0, mask1, w.ah, w.al, w.bh, w.bl, w.uh, w.vh, w.binh,
+                                          overflow, stream);
+    if (rc != FAR_OK) return rc;
+    const float c1 = (float)(1.4426950408889634 / ((double)C * PRESCALE * PRESCALE));
+    const float nrm = (float)(-std::log2((double)L + (double)S));
+    auto gridp = [](long n) { long g = (n + 255) / 256; return (unsigned)(g < 16384 ? (g > 0 ? g : 1) : 16384); };
+    hipLaunchKernelGGL(k_skd_side, dim3(gridp((long)Z * (Lp + Sp))), dim3(256), 0, stream, (const float*)(w.uh + (size_t)iters * Z * Lp),
+                       (const float*)(w.vh + (size_t)iters * Z * Sp), mask0, mask1, Z, L, S, Lp, Sp, nrm, d.pr, d.pc);
+    hipMemsetAsync(d.gmax, 0, (size_t)Z * 4, stream);
+    if (M > 0)
+        hipLaunchKernelGGL(k_skd_pos, dim3(std::min((M + 127) / 128, 2048)), dim3(256), 0, stream, (const _Float16*)w.ah, (const _Float16*)w.al,
+                           (const _Float16*)w.bh, (const _Float16*)w.bl, Z, L, S, Lp, Sp, c1, pb, pi, pj, M, (const float*)d.pr,
+                           (const float*)d.pc, fk, cpos, d.dl, d.dw, d.gmax);
+    const size_t smem = 2 * (2 * PLANE32) + 2 * DT * sizeof(float);
+    FAR_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)k_skd_pass<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+                        hipFuncSetAttribute((const void*)k_skd_pass<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    const int nparts = (Lp / 128) * Z;
+    hipLaunchKernelGGL(k_skd_pass<true>, dim3(nparts), dim3(256), smem, stream, (const _Float16*)w.ah, (const _Float16*)w.al,
+                       (const _Float16*)w.bh, (const _Float16*)w.bl, Z, L, S, Lp, Sp, c1, (const float*)d.pr, (const float*)d.pc, d.u, fk,
+                       d.gmax, d.lossp);
+    hipLaunchKernelGGL(k_skd_pass<false>, dim3((Sp / 128) * Z), dim3(256), smem, stream, (const _Float16*)w.bh, (const _Float16*)w.bl,
+                       (const _Float16*)w.ah, (const _Float16*)w.al, Z, S, L, Sp, Lp, c1, (const float*)d.pc, (const float*)d.pr, d.v, fk,
+                       (unsigned*)nullptr, (double*)nullptr);
+    hipLaunchKernelGGL(k_skd_loss, dim3(1), dim3(256), 0, stream, (const double*)d.lossp, nparts, (const double*)d.dl, M, (double)fk.cneg,
+                       loss_out);
+    return far_check_launch();
+}
+
+int far_sinkhorn_dense_focal_bwd_f16(const float* f0, const float* f1, int Z, int L, int S, int Cc, const float* bin_score, int iters,
+                                     const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj,
+                                     int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, const float* gup,
+                                     float* df0, float* df1, float* dbin, void* ws, hipStream_t stream) {
+    far_clear_errors();
+    if (!f0 || !f1 || !bin_score || !ws || !gup || !df0 || !df1 || !dbin || !dims_ok(Z, L, S, Cc, iters) || M < 0 ||
+        (M > 0 && (!pb || !pi || !pj)))
+        return FAR_EINVAL;
+    const WsT w = carve_t(ws, Z, L, S, iters);
+    const WsD d = carve_d(ws, w.bytes, Z, L, S, M);
+    const int T = iters, Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    FocalK fk;
+    double cpos;
+    make_plan(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt, fk, cpos);
+    hipLaunchKernelGGL(k_skd_seed, dim3(Z), dim3(256), 0, stream, (const float*)d.u, (const float*)d.v, (const float*)d.dw, M, gup, Z, Lp, Sp,
+                       w.ubar + (size_t)T * Z * Lp, w.vbar + (size_t)T * Z * Sp, w.barbin + (size_t)T * 2 * Z, d.wpos);
+    const DenseRun dn{d.pr, d.pc, gup, d.gmax, fk.cneg, fk.alpha, fk.gamma};
+    return skt_backward(w, f0, f1, Z, L, S, bin_score, T, mask0, mask1, pb, pi, pj, M, (const float*)d.wpos, (const float*)nullptr,
+                        (const float*)nullptr, df0, df1, dbin, &dn, stream);
 }
 
 }  // extern "C"

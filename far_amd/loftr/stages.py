@@ -120,15 +120,17 @@ class CoarseMatching(nn.Module):
         """match_type 'sinkhorn' (coarse_matching.py:120-147).  Evaluation: the same data keys as the dual-softmax evaluation path, plus
         conf_matrix_with_bin when materialize_conf is set (conf_matrix is then its [:, :L, :S] view).  Training (or gradients needed) on
         GPU tensors with the sparse labels spv_b/i/j_ids in data: the `if train:` branch below (conf_matrix None; conf_pos, conf_bin0,
-        conf_bin1 from ops.sinkhorn_pos_conf).  Evaluation with the labels in data (val_step): the same three keys, no graph."""
+        conf_bin1 from ops.sinkhorn_pos_conf).  Evaluation with the labels in data (val_step): the same three keys, no graph.
+        Dense supervision (sparse_spvs = False): instead of the three keys the handle data['conf_dense'] (_dense_handle) for
+        ops.sinkhorn_dense_focal_loss -- in evaluation with the prefilter the filtered conf_matrix itself."""
         train = self.training or ag.needs_grad(feat_c0, feat_c1)
         if train:
             if not feat_c0.is_cuda:
                 raise NotImplementedError('Sinkhorn coarse matching: training / gradients through the optimal-transport matcher exist '
                                           'on the GPU only (no differentiable form off it)')
-            if 'spv_b_ids' not in data or not self.config.get('sparse_spvs', True):
-                raise NotImplementedError('Sinkhorn coarse matching: training needs the sparse labels spv_b_ids / spv_i_ids / spv_j_ids '
-                                          'in data (dense supervision is not built)')
+            if 'spv_b_ids' not in data:
+                raise NotImplementedError('Sinkhorn coarse matching: training needs the labels spv_b_ids / spv_i_ids / spv_j_ids in data '
+                                          '(sparse supervision reads them as positions, dense supervision as the positives)')
             if self.materialize_conf:
                 raise NotImplementedError('Sinkhorn coarse matching: training never builds the dense conf_matrix_with_bin '
                                           '(materialize_conf is for evaluation)')
@@ -151,6 +153,8 @@ class CoarseMatching(nn.Module):
         scale = data['hw0_i'][0] / data['hw0_c'][0]
         s0 = data['scale0'].float().contiguous() if 'scale0' in data else None
         s1 = data['scale1'].float().contiguous() if 'scale1' in data else None
+        dense = not self.config.get('sparse_spvs', True)
+        data.pop('conf_dense', None)
         if train:
             # The sparse loss of this configuration (loftr_loss.py:86-119) reads the coupling matrix at the ground-truth positions and
             # at its dustbin column / row only, so no (N, L+1, S+1) tensor is built: the matcher selects the predicted matches under
@@ -164,6 +168,15 @@ class CoarseMatching(nn.Module):
                                                 scale, as_u8(mask_c0), as_u8(mask_c1), self._valid_hw(data), None, None,
                                                 prefilter=False)
                 picked = self._sample_train(out['b_ids'], out['i_ids'], out['j_ids'], out['mconf'], data, feat_c0.shape[0])
+            if dense:
+                # dense supervision (sparse_spvs = False: the loftr_ot_dense configurations; loftr_loss.py:121-127 reads EVERY entry
+                # of conf = P[:, :L, :S]).  Still no matrix: the loss module gets a handle on the two in-graph feature maps and the
+                # in-graph bin_score and evaluates ops.sinkhorn_dense_focal_loss with its own alpha / gamma / weights.
+                data.update({'conf_matrix': None, 'conf_dense': self._dense_handle(feat_c0, feat_c1, self.bin_score, mask_c0, mask_c1)})
+                for k in ('conf_pos', 'conf_bin0', 'conf_bin1', 'conf_matrix_with_bin'):
+                    data.pop(k, None)
+                data.update(**picked)
+                return
             pos, bin0, bin1 = ops.sinkhorn_pos_conf(feat_c0, feat_c1, self.bin_score, self.skh_iters, data['spv_b_ids'],
                                                     data['spv_i_ids'], data['spv_j_ids'], as_u8(mask_c0), as_u8(mask_c1))
             data.update({'conf_matrix': None, 'conf_pos': pos, 'conf_bin0': bin0, 'conf_bin1': bin1})
@@ -175,7 +188,17 @@ class CoarseMatching(nn.Module):
                                         self.thr, self.border_rm, data['hw0_c'], data['hw1_c'], scale, as_u8(mask_c0),
                                         as_u8(mask_c1), self._valid_hw(data), s0, s1, prefilter=self.skh_prefilter,
                                         want_conf=self.materialize_conf or (spv and self.skh_prefilter), overlap=overlap)
-        if spv:
+        if spv and dense:
+            # validation of a dense-supervision configuration.  Prefilter off: the handle with detached tensors, the loss module runs the
+            # forward kernels only.  Prefilter on: the reference's loss sees the FILTERED matrix (coarse_matching.py:135-142), so the
+            # matcher's materialised filtered conf_matrix stays in data and the loss module evaluates its torch form on it.
+            for k in ('conf_pos', 'conf_bin0', 'conf_bin1'):
+                data.pop(k, None)
+            if self.skh_prefilter:
+                out['conf_matrix_with_bin'] = None
+            else:
+                data['conf_dense'] = self._dense_handle(feat_c0.detach(), feat_c1.detach(), self.bin_score.detach(), mask_c0, mask_c1)
+        elif spv:
             # validation (the matcher in eval mode, then the loss): the three groups of entries the loss reads, no graph.  With the
             # prefilter the loss sees the filtered matrix (the reference clones conf_matrix_with_bin after the in-place filter,
             # coarse_matching.py:135-142): the positions are read from the matcher's own filtered output
@@ -206,6 +229,13 @@ class CoarseMatching(nn.Module):
             data['conf_matrix_with_bin'] = out['conf_matrix_with_bin']
         else:
             data.pop('conf_matrix_with_bin', None)
+
+    def _dense_handle(self, feat_c0, feat_c1, bin_score, mask_c0, mask_c1):
+        """data['conf_dense'] of the optimal-transport matcher: what losses.coarse_focal_loss_dense hands to
+        ops.sinkhorn_dense_focal_loss (match_type tells it from the dual-softmax handle)."""
+        as_u8 = lambda m: None if m is None else m.to(torch.uint8).contiguous()
+        return {'match_type': 'sinkhorn', 'feat_c0': feat_c0, 'feat_c1': feat_c1, 'bin_score': bin_score, 'skh_iters': self.skh_iters,
+                'mask0': as_u8(mask_c0), 'mask1': as_u8(mask_c1)}
 
     # ------------------------------------------------------------------------------------------------------
     # training (coarse_matching.py:86-147 + :199-240).  The coarse loss of this configuration (dual-softmax, sparse

@@ -150,11 +150,18 @@ def coarse_focal_loss_dense_torch(conf, ids, no_gt, alpha=FOCAL_ALPHA, gamma=FOC
 
 
 def coarse_focal_loss_dense(data, alpha=FOCAL_ALPHA, gamma=FOCAL_GAMMA, pos_weight=POS_WEIGHT, neg_weight=NEG_WEIGHT):
-    """The coarse loss of the *_dense configurations (sparse_spvs = False, dual_softmax, focal).  GPU training / validation path:
+    """The coarse loss of the *_dense configurations (sparse_spvs = False, focal).  GPU training / validation path:
     data['conf_dense'] (CoarseMatching: the two coarse feature maps, the temperature, the masks) -> ops.coarse_dense_focal_loss, one
-    scalar with a HIP backward and no L x S tensor.  Otherwise a dense data['conf_matrix'] is evaluated in torch, the positives given
+    scalar with a HIP backward and no L x S tensor; a handle with match_type 'sinkhorn' (feature maps, bin_score, skh_iters, masks)
+    -> ops.sinkhorn_dense_focal_loss.  Otherwise a dense data['conf_matrix'] is evaluated in torch, the positives given
     as spv ids or as conf_matrix_gt, the weight from data['mask0'] / ['mask1'] (compute_c_weight, :190-196)."""
     h = data.get('conf_dense')
+    if h is not None and h.get('match_type') == 'sinkhorn':
+        # the optimal-transport matcher (loftr_ot_dense): the handle also carries the in-graph bin_score and skh_iters
+        from . import ops
+        return ops.sinkhorn_dense_focal_loss(h['feat_c0'], h['feat_c1'], h['bin_score'], h['skh_iters'], data['spv_b_ids'],
+                                             data['spv_i_ids'], data['spv_j_ids'], alpha, gamma, pos_weight, neg_weight, h['mask0'],
+                                             h['mask1'], no_gt=has_no_ground_truth(data))
     if h is not None:
         from . import ops
         return ops.coarse_dense_focal_loss(h['feat_c0'], h['feat_c1'], data['spv_b_ids'], data['spv_i_ids'], data['spv_j_ids'],
@@ -214,23 +221,27 @@ def rt_loss(expec_rt, T_0to1, regress_rt=True, l1=True):
 class LoFTRLoss(torch.nn.Module):
     """Counterpart of src/losses/loftr_loss.py:LoFTRLoss for the FAR training configurations (dual_softmax, focal coarse
     loss, sparse supervision; l2_with_std fine loss; 6D pose loss), the Sinkhorn matcher's sparse loss and the dense supervision of
-    the dual-softmax matcher (sparse_spvs = False: coarse_focal_loss_dense).  Same constructor argument (the lower-cased config
+    the dual-softmax matcher (sparse_spvs = False: coarse_focal_loss_dense) -- and, with LoFTRLoss(config, ot_dense=True), of the
+    Sinkhorn matcher.  Same constructor argument (the lower-cased config
     with ['loftr']['loss'], ['loftr']['match_coarse'], ...) and the same effect: forward(data) writes data['loss'] and
     data['loss_scalars'].  On the GPU training path the coarse term reads data['conf_pos'] (K1's sparse HIP kernels);
     with a dense data['conf_matrix'] it gathers the same positions from it (given as spv ids or as conf_matrix_gt)."""
 
-    def __init__(self, config):
+    def __init__(self, config, *, ot_dense=False):
+        """ot_dense (keyword only): accept match_type 'sinkhorn' with sparse_spvs = False (the loftr_ot_dense configurations:
+        ops.sinkhorn_dense_focal_loss).  Opt-in, because the plain constructor's refusal of that configuration is pinned by tests."""
         super().__init__()
         self.config = config
         lc = self.loss_config = config['loftr']['loss']
         mc = config['loftr']['match_coarse']
         self.sparse_spvs = bool(mc.get('sparse_spvs', True))
         if (mc['match_type'] not in ('dual_softmax', 'sinkhorn') or lc['coarse_type'] != 'focal'
-                or (not self.sparse_spvs and mc['match_type'] != 'dual_softmax')):
+                or (not self.sparse_spvs and mc['match_type'] != 'dual_softmax' and not ot_dense)):
             raise NotImplementedError('far_amd.losses.LoFTRLoss covers dual_softmax / sinkhorn + focal + sparse supervision '
                                       '(the FAR training scripts, the loftr_ot configurations) and dual_softmax + focal + dense '
                                       'supervision (the loftr_ds_dense configurations); cross-entropy and dense supervision of the '
-                                      'Sinkhorn matcher are not built')
+                                      'Sinkhorn matcher are not built -- the latter (the loftr_ot_dense configurations) is accepted '
+                                      'with the keyword LoFTRLoss(config, ot_dense=True)')
         self.match_type = mc['match_type']
         self.correct_thr = lc['fine_correct_thr']
         self.c_pos_w = lc['pos_weight']

@@ -324,6 +324,78 @@ def sinkhorn_pos_conf(f0, f1, bin_score, iters, pb, pi, pj, mask0=None, mask1=No
     return _SinkhornPosConf.apply(f0, f1, bin_score, pb, pi, pj, mask0, mask1, iters)
 
 
+class _SinkhornDenseFocal(torch.autograd.Function):
+    """The dense-supervision focal loss on the optimal-transport coupling matrix (loftr_loss.py:121-127 on conf = P[:, :L, :S]) as ONE
+    scalar, differentiable w.r.t. both coarse feature maps and bin_score, without P or any other L x S tensor
+    (far_sinkhorn_dense_focal_f16s / far_sinkhorn_dense_focal_bwd_f16)."""
+
+    @staticmethod
+    def forward(ctx, f0, f1, bin_score, pb, pi, pj, mask0, mask1, iters, alpha, gamma, pos_weight, neg_weight, no_gt):
+        lib = _lib.load()
+        Z, L, C = f0.shape
+        S = f1.shape[1]
+        dev = f0.device
+        f0c, f1c = f0.detach().float().contiguous(), f1.detach().float().contiguous()
+        bs = bin_score.detach().float().contiguous()
+        m0 = None if mask0 is None else mask0.reshape(Z, L).to(torch.uint8).contiguous()
+        m1 = None if mask1 is None else mask1.reshape(Z, S).to(torch.uint8).contiguous()
+        if no_gt:
+            # loftr_loss.py:65-70: the labels are ignored; in the weighted case the dummy entry (0, 0, 0) leaves the negative term too
+            pb = pi = pj = torch.zeros(1 if (m0 is not None or m1 is not None) else 0, dtype=torch.int64, device=dev)
+        else:
+            pb, pi, pj = (t.to(device=dev, dtype=torch.int64).contiguous() for t in (pb, pi, pj))
+        M = int(pb.numel())
+        ws = _ws(lib.far_sinkhorn_dense_focal_workspace_bytes(Z, L, S, C, iters, M), dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        ctx.args = (Z, L, S, C)
+        ctx.iters = iters
+        ctx.focal = (float(alpha), float(gamma), float(pos_weight), float(neg_weight), int(bool(no_gt)))
+        rc = lib.far_sinkhorn_dense_focal_f16s(_p(f0c, torch.float32), _p(f1c, torch.float32), Z, L, S, C, _p(bs, torch.float32), iters,
+                                               _p(m0), _p(m1), _p(pb), _p(pi), _p(pj), M, *ctx.focal, _p(loss), _p(ws),
+                                               _p(overflow_flag(dev)), _stream())
+        _lib.check(rc, 'far_sinkhorn_dense_focal_f16s')
+        ctx.save_for_backward(f0c, f1c, bs, pb, pi, pj, ws)
+        ctx.masks = (m0, m1)
+        ctx.bin_shape = bin_score.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        f0c, f1c, bs, pb, pi, pj, ws = ctx.saved_tensors
+        m0, m1 = ctx.masks
+        gup = g.detach().float().reshape(1).contiguous()                      # stays on the device: no host read
+        df0, df1 = torch.empty_like(f0c), torch.empty_like(f1c)
+        dbin = torch.empty(1, dtype=torch.float32, device=f0c.device)
+        rc = lib.far_sinkhorn_dense_focal_bwd_f16(_p(f0c), _p(f1c), *ctx.args, _p(bs), ctx.iters, _p(m0), _p(m1), _p(pb), _p(pi), _p(pj),
+                                                  int(pb.numel()), *ctx.focal, _p(gup, torch.float32), _p(df0), _p(df1), _p(dbin), _p(ws),
+                                                  _stream())
+        _lib.check(rc, 'far_sinkhorn_dense_focal_bwd_f16')
+        return (df0, df1, dbin.reshape(ctx.bin_shape)) + (None,) * 11
+
+
+def sinkhorn_dense_focal_loss(f0, f1, bin_score, iters, pb, pi, pj, alpha, gamma, pos_weight, neg_weight, mask0=None, mask1=None,
+                              no_gt=False):
+    """The optimal-transport matcher trained with dense coarse supervision (match_type 'sinkhorn', sparse_spvs = False, focal:
+    loftr_loss.py:56-75, :121-127): the loss over EVERY entry of conf = P[:, :L, :S], P the coupling matrix of
+    ops.coarse_match_sinkhorn (no prefilter), as a 0-dim fp32 tensor with a HIP backward to f0, f1 and bin_score (the gradient of the
+    unrolled iterations under a dense dloss/dlogP).  Positives = the labels (pb, pi, pj), each one positive term; negatives = every
+    other entry; mask0 (Z, L) / mask1 (Z, S): padded batches (loss weight mask0 x mask1).  no_gt: not one ground-truth match (the
+    labels are ignored).  Nothing of size L x S is allocated.  C must be 256, 0 <= iters <= 48."""
+    if not (f0.is_cuda and f1.is_cuda and bin_score.is_cuda):
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    Z, L, C = f0.shape
+    S = f1.shape[1]
+    iters = int(iters)
+    if C != 256:
+        raise NotImplementedError('the Sinkhorn coarse matcher has kernels for C = 256 only')
+    if not 0 <= iters <= SINKHORN_MAX_ITERS:
+        raise NotImplementedError(f'training through the Sinkhorn matcher is built for 0 <= skh_iters <= {SINKHORN_MAX_ITERS}')
+    if Z == 0 or L == 0 or S == 0:         # nothing to launch: a zero that still hangs in the graph
+        return (f0.sum() + f1.sum() + bin_score.sum()) * 0.0
+    return _SinkhornDenseFocal.apply(f0, f1, bin_score, pb, pi, pj, mask0, mask1, iters, alpha, gamma, pos_weight, neg_weight, no_gt)
+
+
 def coarse_pos_conf(f0, f1, pb, pi, pj, temperature):
     """K1, training: conf_matrix[pb, pi, pj] (M,) fp32 with a HIP backward to both feature maps; C must be 256."""
     if not f0.is_cuda:

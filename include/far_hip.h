@@ -214,6 +214,30 @@ int far_coarse_dense_focal_bwd_f16(const float* f0, const float* f1, int Z, int 
                                    int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, const float* gup,
                                    int split_g, float* df0, float* df1, void* ws, far_stream_t stream);
 
+/* The optimal-transport matcher with DENSE coarse supervision (sinkhorn_train_f16s.hip): match_type 'sinkhorn', coarse_type 'focal',
+ * sparse_spvs = False (src/losses/loftr_loss.py:56-75, :87-89, :121-127; the loftr_ot_dense configurations).  The focal loss of
+ * far_coarse_dense_focal_f16s over EVERY entry of conf = P[:, :L, :S] of the coupling matrix (the dustbin row and column are not
+ * supervised), without P or any other tensor of size L S.  Arguments as far_sinkhorn_pos_conf_f16s (bin_score: one device float;
+ * masks optional; 0 <= iters <= 48; C must be 256) and far_coarse_dense_focal_f16s (labels, focal constants).  Each of the M labels is
+ * one positive term (a label out of range or on a masked cell is not read and adds nothing; all M count in the normalisers).
+ * no_gt != 0 (:65-70): the positive term has weight 0 and Z L S entries normalise the negative term; the labels handed over then only
+ * leave the negative term (the caller passes the dummy entry (0, 0, 0) for a batch with masks, none otherwise).
+ * ws: far_sinkhorn_dense_focal_workspace_bytes(Z, L, S, C, iters, M) bytes (0: unsupported shape), kept untouched between the
+ * forward and the backward call.  forward: the matcher's own iterations (the bits of inference), loss_out = one device float. */
+size_t far_sinkhorn_dense_focal_workspace_bytes(int Z, int L, int S, int C, int iters, int M);
+int far_sinkhorn_dense_focal_f16s(const float* f0, const float* f1, int Z, int L, int S, int C, const float* bin_score, int iters,
+                                  const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj,
+                                  int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, float* loss_out,
+                                  void* ws, int* overflow, far_stream_t stream);
+/* backward: the same arguments as the forward call; gup = one device float (dL/dloss), never read by the host.  df0 (Z, L, C),
+ * df1 (Z, S, C) and dbin (one float: dL/d bin_score, non-zero although the dustbins carry no loss term) are overwritten; masked rows
+ * get exactly 0.  The adjoint recursion of far_sinkhorn_pos_conf_bwd_f16 seeded with the dense G = (dloss/dp) p; no float atomics:
+ * the same bits at every launch. */
+int far_sinkhorn_dense_focal_bwd_f16(const float* f0, const float* f1, int Z, int L, int S, int C, const float* bin_score, int iters,
+                                     const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj,
+                                     int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, const float* gup,
+                                     float* df0, float* df1, float* dbin, void* ws, far_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------------
  * K2  EMM head: bilinear dual-softmax attention  F = v~^T (softmax_row(s) * softmax_col(s)) v~
  * replaces src/loftr/loftr_module/transformer.py:275-292 (CrossAttention.forward), one call per direction

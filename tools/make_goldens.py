@@ -2,8 +2,8 @@
 
 Container-only: needs /root/reference and tools/ref_shim.py.  The fixtures are data (seeds, small inputs,
 expected outputs); no reference source is copied.  Weights come from far_amd.synth (seeded), inputs from
-seeds recorded in each file.  Run:  python tools/make_goldens.py  (all of g1 ... g18 and g20 ... g23; `python tools/make_goldens.py g20`
-for one; g19 comes from tools/make_golden_vit.py).  g23 = the dense-supervision focal loss (sparse_spvs = False) with its gradient.  g21 = the full softmax attention core, layer and stack (attention = 'full').  g20 = LoFTR.forward off the default launch sequence of far_amd (unequal image
+seeds recorded in each file.  Run:  python tools/make_goldens.py  (all of g1 ... g18 and g20 ... g24; `python tools/make_goldens.py g20`
+for one; g19 comes from tools/make_golden_vit.py).  g24 = the optimal-transport matcher with dense supervision (CoarseMatching + compute_coarse_loss, gradients to the features and bin_score).  g23 = the dense-supervision focal loss (sparse_spvs = False) with its gradient.  g21 = the full softmax attention core, layer and stack (attention = 'full').  g20 = LoFTR.forward off the default launch sequence of far_amd (unequal image
 sizes, padded masks, scales), with the fp32 run's deviation from the float64 oracle stored next to it.
 """
 import importlib.util
@@ -868,6 +868,83 @@ def g23_dense_focal():
     print('g23:', {k: float(v) for k, v in out.items() if k.startswith('loss')})
 
 
+def _log_optimal_transport(scores, alpha, iters):
+    """The operator the reference's CoarseMatching imports from a superglue.py that is not in its tree (coarse_matching.py:75),
+    restated from its definition (log-domain Sinkhorn with a dustbin row and column, uniform marginals with the
+    dustbins taking the other side's count): -> log of the coupling matrix, (N, L+1, S+1)."""
+    N, L, S = scores.shape
+    a = alpha.expand(N, L, 1)
+    Zc = torch.cat([torch.cat([scores, a], 2), alpha.expand(N, 1, S + 1)], 1)
+    norm = -torch.log(scores.new_tensor(float(L + S)))
+    lmu = torch.cat([norm.expand(L), torch.log(scores.new_tensor(float(S)))[None] + norm])
+    lnu = torch.cat([norm.expand(S), torch.log(scores.new_tensor(float(L)))[None] + norm])
+    u, v = torch.zeros(N, L + 1, dtype=scores.dtype), torch.zeros(N, S + 1, dtype=scores.dtype)
+    for _ in range(iters):
+        u = lmu - torch.logsumexp(Zc + v[:, None, :], 2)
+        v = lnu - torch.logsumexp(Zc + u[:, :, None], 1)
+    return Zc + u[:, :, None] + v[:, None, :] - norm
+
+
+def g24_ot_dense():
+    """The reference's own CoarseMatching.forward (match_type 'sinkhorn', sparse_spvs = False, training mode; coarse_matching.py:105-147)
+    followed by LoFTRLoss.compute_coarse_loss (loftr_loss.py:56-75, :121-127): N = 2, grids 6 x 8 and 5 x 7, skh_iters = 3; plain, padded
+    masks, no ground truth.  Each case: the loss and its gradients w.r.t. both feature maps and bin_score.  The Sinkhorn operator
+    itself is `_log_optimal_transport` above (the reference's tree lacks the file it imports it from).  Data only."""
+    import types
+    from tests.test_sinkhorn_gpu import features
+    sg = types.ModuleType('src.loftr.utils.superglue')
+    sg.log_optimal_transport = _log_optimal_transport
+    sys.modules['src.loftr.utils.superglue'] = sg
+    from src.loftr.utils.coarse_matching import CoarseMatching
+    from src.losses.loftr_loss import LoFTRLoss
+    from far_amd.config import far_train_config
+    cfg = far_train_config()
+    cfg['loftr']['match_coarse'].update(match_type='sinkhorn', sparse_spvs=False, skh_iters=3, train_pad_num_gt_min=2)
+    cfg['loftr']['loss']['neg_weight'] = 0.7
+    lf = LoFTRLoss(cfg).train()
+    N, hw0, hw1, seed = 2, (6, 8), (5, 7), 124
+    L, S = hw0[0] * hw0[1], hw1[0] * hw1[1]
+    f0, f1, pairs = features(N, L, S, seed=seed, share=0.8)
+    rng = np.random.default_rng(seed)
+    gt = np.zeros((N, L, S), np.float32)
+    for n, (src, dst) in enumerate(pairs):
+        keep = rng.random(len(src)) < 0.8
+        gt[n, src[keep], dst[keep]] = 1.0
+    m0 = np.zeros((N,) + hw0, bool)
+    m1 = np.zeros((N,) + hw1, bool)
+    m0[0, :5, :8] = True; m0[1, :6, :6] = True
+    m1[0, :5, :5] = True; m1[1, :4, :7] = True
+    m0, m1 = m0.reshape(N, L), m1.reshape(N, S)
+    weight = (m0[..., None] * m1[:, None]).astype(np.float32)
+    gt_w = gt * weight                                      # ground truth of the padded batch: on valid cells only
+    out = {}
+    for tag, g, masked in (('plain', gt, False), ('weight', gt_w, True), ('nogt', np.zeros_like(gt), False), ('nogt_weight', np.zeros_like(gt), True)):
+        torch.manual_seed(seed)
+        cm = CoarseMatching(cfg['loftr']['match_coarse']).train()
+        t0 = torch.from_numpy(f0.copy()).requires_grad_(True)
+        t1 = torch.from_numpy(f1.copy()).requires_grad_(True)
+        b, i, j = np.nonzero(g)
+        if len(b) == 0:
+            b = i = j = np.zeros(1, np.int64)                # spvs_coarse's dummy entry (supervision.py:122-128)
+        data = {'hw0_i': (8 * hw0[0], 8 * hw0[1]), 'hw1_i': (8 * hw1[0], 8 * hw1[1]), 'hw0_c': hw0, 'hw1_c': hw1,
+                'spv_b_ids': torch.from_numpy(b), 'spv_i_ids': torch.from_numpy(i), 'spv_j_ids': torch.from_numpy(j)}
+        mm = (torch.from_numpy(m0.copy()), torch.from_numpy(m1.copy())) if masked else (None, None)
+        if masked:
+            data.update(mask0=mm[0].reshape(N, *hw0), mask1=mm[1].reshape(N, *hw1))
+        cm(t0, t1, data, *mm)
+        assert 'conf_matrix_with_bin' not in data and data['conf_matrix'].shape == (N, L, S)
+        loss = lf.compute_coarse_loss(data['conf_matrix'], torch.from_numpy(g.copy()), torch.from_numpy(weight.copy()) if masked else None)
+        loss.backward()
+        out['loss_' + tag] = loss.detach().numpy()
+        out['df0_' + tag], out['df1_' + tag] = t0.grad.numpy(), t1.grad.numpy()
+        out['dbin_' + tag] = cm.bin_score.grad.numpy()
+        if tag == 'plain':
+            out['conf_plain'] = data['conf_matrix'].detach().numpy()
+    save('g24_ot_dense', seed=seed, neg_weight=np.float32(0.7), skh_iters=3, bin_score=np.float32(cfg['loftr']['match_coarse']['skh_init_bin_score']),
+         f0=f0, f1=f1, gt=gt.astype(np.int8), gt_weight=gt_w.astype(np.int8), mask0=m0, mask1=m1, **out)
+    print('g24:', {k: float(v) for k, v in out.items() if k.startswith(('loss', 'dbin'))})
+
+
 def g8_manifest(m):
     man = {k: list(v.shape) for k, v in m.state_dict().items()}
     with open(os.path.join(OUT, 'g8_state_dict_manifest.json'), 'w') as f:
@@ -920,6 +997,9 @@ if __name__ == '__main__':
     if len(sys.argv) > 1 and sys.argv[1] == 'g23':
         g23_dense_focal()
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == 'g24':
+        g24_ot_dense()
+        sys.exit(0)
     g1_coarse()
     g9_metrics()
     g5_solver()
@@ -943,3 +1023,4 @@ if __name__ == '__main__':
     g21_full_attention()
     g22_sinkhorn_loss()
     g23_dense_focal()
+    g24_ot_dense()
