@@ -30,7 +30,7 @@ typedef struct ihipStream_t* far_stream_t; /* == hipStream_t */
 
 /* ABI version of this header; bumped when a signature changes (2: activation exponent / overflow flag of K9, K13, K14; 3: the
  * far_wino_* / far_conv3x3_wino_f32 entry points, 16 tuning keys; 4: far_upsample2x_bwd_f32, far_fine_scatter_det_f32, far_bn_train_*, far_adamw_*; 5: far_linear_kv_f16s, far_linear_q_apply_f16s,
- * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way).  far_amd/_lib.py refuses a library whose version differs. */
+ * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way, and so were far_grad_norm_workspace_bytes, far_grad_norm_f32, far_grad_clip_scale_f32 and far_adam_step_f32).  far_amd/_lib.py refuses a library whose version differs. */
 int far_abi_version(void);
 /* Id of the sources the library was built from: sha256/16 over far_amd/csrc/* and the compiler flags (far_amd/build.py
  * source_id()).  far_amd/_lib.py refuses a library whose id differs from the sources it sits next to. */
@@ -475,6 +475,24 @@ int far_upsample2x_add_f32(const float* lo, const float* hi, int N, int h, int w
 long far_adamw_table_bytes(int n, long nblocks);
 int far_adamw_step_f32(const void* table, int n, long nblocks, double lr, double beta1, double beta2, double eps, double wd, double bc1,
                        double bc2_sqrt, far_stream_t stream);
+/* Gradient clipping by the global norm on K20's table (pytorch-lightning's gradient_clip_val, train.py:339 / default.py:166 = 0.5;
+ * torch.nn.utils.clip_grad_norm_), without a host synchronisation and deterministic (fixed-order trees, float64 sums of exact squares,
+ * no atomics).  workspace: far_grad_norm_workspace_bytes(nblocks) device bytes, zeroed once by the caller: a result block
+ * { float norm; float coef; int32 nonfinite; int32 skipped; } at byte 0, one float64 partial per workgroup from byte 64.
+ *   far_grad_norm_f32: partial norms of the table into partials[first .. first + nblocks); when total > 0 a second launch combines
+ *     partials[0 .. total) and writes norm (rounded to fp32 once), coef = min(max_norm / (norm + 1e-6), 1) in fp32 as torch forms it
+ *     (a NaN norm gives a NaN coef), nonfinite = norm is NaN or inf, and skipped += 1 when count_skipped != 0 and nonfinite.  Several
+ *     tables share one norm: each passes its own `first`, the last one `total`.  norm_type: 2 or +inf (max |g|, a NaN survives).
+ *   far_grad_clip_scale_f32: g *= coef in place (the stand-alone far_amd.optim.clip_grad_norm_).
+ *   far_adam_step_f32: far_adamw_step_f32's step with coupled != 0 -> torch.optim.Adam (g += wd p instead of p *= 1 - lr wd);
+ *     clip_workspace != NULL -> every gradient is multiplied by coef on its way in (p.grad itself is not modified; bit-identical to
+ *     far_grad_clip_scale_f32 followed by the plain step) and, with skip_nonfinite != 0, p, m, v stay untouched when nonfinite is set. */
+size_t far_grad_norm_workspace_bytes(long nblocks);
+int far_grad_norm_f32(const void* table, int n, long nblocks, long first, long total, double norm_type, double max_norm,
+                      int count_skipped, void* workspace, far_stream_t stream);
+int far_grad_clip_scale_f32(const void* table, int n, long nblocks, const void* workspace, far_stream_t stream);
+int far_adam_step_f32(const void* table, int n, long nblocks, double lr, double beta1, double beta2, double eps, double wd, double bc1,
+                      double bc2_sqrt, int coupled, const void* clip_workspace, int skip_nonfinite, far_stream_t stream);
 
 /* K19: BatchNorm2d with BATCH statistics (training mode) on channels_last fp32 tensors [M = N H W][C], C % 4 == 0, C <= 1024
  * (batchnorm_train_f32.hip) -- resnet_fpn.py:24-41, 60-62, 75-91 under autograd; deterministic (fixed-order two-stage sums).
