@@ -98,6 +98,11 @@ SIGNATURES = {
     'far_bn_act_train_fwd_f32': (c_i, [c_p, c_p, c_l, c_i, c_p, c_p, c_f, c_f, c_p, c_p, c_i, c_f, c_p, c_p, c_p, c_l, c_p]),
     'far_bn_train_stats_f32': (c_i, [c_p, c_l, c_i, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_p]),
     'far_bn_train_bwd_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_p, c_l, c_p]),
+    'far_bn_sync_moments_f32': (c_i, [c_p, c_l, c_i, c_p, c_p, c_l, c_p]),
+    'far_bn_sync_stats_f32': (c_i, [c_p, c_i, c_i, c_p, c_p, c_f, c_f, c_p, c_p, c_p, c_p]),
+    'far_bn_sync_apply_f32': (c_i, [c_p, c_p, c_l, c_i, c_p, c_i, c_f, c_p, c_p]),
+    'far_bn_sync_bwd_sums_f32': (c_i, [c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_f, c_p, c_p, c_p, c_p, c_l, c_p]),
+    'far_bn_sync_bwd_dx_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_f, c_p, c_p, c_p, c_p]),
     'far_conv_packed_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     'far_conv_pack_f32': (c_i, [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),
     'far_weight_scale_f32': (c_i, [c_p, c_l, c_p, c_p]),

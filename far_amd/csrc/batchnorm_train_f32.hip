@@ -13,6 +13,11 @@
 //           dx = gamma rstd (g - dbeta / M - xhat dgamma / M);  the residual's gradient is g.
 // Sums: every workgroup adds a contiguous range of pixels per channel in fp32 around a per-range shift (the range's first pixel:
 // no cancellation between a large mean and a small variance), the ranges are combined in float64 in a fixed order (four quarter sums per channel, then their sum).
+//
+// The synchronised form (torch.nn.SyncBatchNorm: mp3d_loftr/train.py:342 converts all 17 layers, the statistics span the ranks) is the
+// same arithmetic cut where the ranks meet -- far_bn_sync_*: local moments { n, sum x, sum x^2 } as a float64 record -> [exchange by the
+// caller] -> global statistics from the stacked records (added in rank order) -> apply; local { sum g, sum g xhat } -> [exchange] -> dx.
+// With one record the results are the bits of the calls above.
 #include "common.h"
 
 namespace {
@@ -127,12 +132,16 @@ __global__ __launch_bounds__(BN_THREADS) void k_bn_finalize_bwd(const float* __r
     if (j == 0 && c < C) { dbeta[c] = (float)sg; dgamma[c] = (float)sgx; }
 }
 
-// dx = gamma rstd (g - dbeta / M - xhat dgamma / M); dres = g (optional); g = dy act'(y)
+// dx = gamma rstd (g - dbeta / M - xhat dgamma / M); dres = g (optional); g = dy act'(y).  DEVM: 1 / M is read from invM_dev (the
+// synchronised form: M spans the ranks and is known on the device only), else it is the argument.
+template <bool DEVM>
 __global__ __launch_bounds__(256) void k_bn_bwd_dx(const float4* __restrict__ x, const float4* __restrict__ dy, const float4* __restrict__ y,
                                                    const float* __restrict__ mean, const float* __restrict__ rstd,
                                                    const float* __restrict__ gamma, const float* __restrict__ dgamma,
-                                                   const float* __restrict__ dbeta, long nvec, int cvec, float invM, int act, float slope,
+                                                   const float* __restrict__ dbeta, long nvec, int cvec, float invM_arg,
+                                                   const float* __restrict__ invM_dev, int act, float slope,
                                                    float4* __restrict__ dx, float4* __restrict__ dres) {
+    const float invM = DEVM ? *invM_dev : invM_arg;
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += stride) {
         const int c4 = (int)(i % cvec);
@@ -175,6 +184,65 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float4* __restrict__ x, 
         }
         y[i] = v;
     }
+}
+
+// ---- the synchronised form -------------------------------------------------------------------------------------------------------
+
+// one rank's record { n, sum x, sum x^2 }[C] in float64: the sums k_bn_finalize_fwd forms (bn_combine<0>), written out instead of used
+__global__ __launch_bounds__(BN_THREADS) void k_bn_sync_moments(const float* __restrict__ part, int nparts, long M, long per, int C,
+                                                                double* __restrict__ rec) {
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), j = threadIdx.x >> 6;
+    double sx, sxx;
+    bn_combine<0>(part, nparts, M, per, C, c, j, sx, sxx);
+    if (j == 0 && c < C) { rec[c] = (double)M; rec[C + c] = sx; rec[2 * C + c] = sxx; }
+}
+
+// global statistics from the stacked records [W][3][C], added in rank order: k_bn_finalize_fwd's expressions with M = sum n_r.
+// vec: { scale, shift, mean, rstd }[C], then { 1 / M (the backward's factor), 0, 0, 0 }.  One thread per channel.
+__global__ __launch_bounds__(64) void k_bn_sync_stats(const double* __restrict__ recs, int W, int C, const float* __restrict__ gamma,
+                                                      const float* __restrict__ beta, float eps, float momentum,
+                                                      float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                      float* __restrict__ vec) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    double Md = recs[c], sx = recs[C + c], sxx = recs[2 * C + c];
+    for (int r = 1; r < W; ++r) {
+        const double* q = recs + (long)r * 3 * C;
+        Md += q[c]; sx += q[C + c]; sxx += q[2 * C + c];
+    }
+    const double m = sx / Md;
+    double var = sxx / Md - m * m;
+    var = var > 0.0 ? var : 0.0;
+    const double rs = 1.0 / sqrt(var + (double)eps);
+    const float g = gamma ? gamma[c] : 1.f, bt = beta ? beta[c] : 0.f;
+    vec[c] = (float)((double)g * rs);
+    vec[C + c] = (float)((double)bt - m * (double)g * rs);
+    vec[2 * C + c] = (float)m;
+    vec[3 * C + c] = (float)rs;
+    if (running_mean) running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * m);
+    if (running_var) running_var[c] = (float)((1.0 - momentum) * running_var[c] + momentum * (Md > 1.0 ? var * Md / (Md - 1.0) : var));
+    if (c == 0) { vec[4 * C] = __fdiv_rn(1.0f, (float)Md); vec[4 * C + 1] = vec[4 * C + 2] = vec[4 * C + 3] = 0.f; }
+}
+
+// one rank's record { sum g, sum g xhat }[C] in float64 (bn_combine<1>); rounded to fp32 they are this rank's dbeta / dgamma
+__global__ __launch_bounds__(BN_THREADS) void k_bn_sync_bwd_sums(const float* __restrict__ part, int nparts, int C, double* __restrict__ rec,
+                                                                 float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    const int c = blockIdx.x * 64 + (threadIdx.x & 63), j = threadIdx.x >> 6;
+    double sg, sgx;
+    bn_combine<1>(part, nparts, 0, 0, C, c, j, sg, sgx);
+    if (j == 0 && c < C) { rec[c] = sg; rec[C + c] = sgx; dbeta[c] = (float)sg; dgamma[c] = (float)sgx; }
+}
+
+// the stacked records [W][2][C] added in rank order -> sums { sum g, sum g xhat }[C] over all ranks in fp32 (what k_bn_bwd_dx reads)
+__global__ __launch_bounds__(64) void k_bn_sync_bwd_total(const double* __restrict__ recs, int W, int C, float* __restrict__ sums) {
+    const int c = blockIdx.x * 64 + threadIdx.x;
+    if (c >= C) return;
+    double sg = recs[c], sgx = recs[C + c];
+    for (int r = 1; r < W; ++r) {
+        const double* q = recs + (long)r * 2 * C;
+        sg += q[c]; sgx += q[C + c];
+    }
+    sums[c] = (float)sg; sums[C + c] = (float)sgx;
 }
 
 inline int bn_parts(long M) {
@@ -245,9 +313,85 @@ int far_bn_train_bwd_f32(const float* x, const float* dy, const float* y, const 
     const long nvec = M * (C / 4);
     long blocks = (nvec + 255) / 256;
     blocks = blocks > 4096 ? 4096 : blocks;
-    hipLaunchKernelGGL(k_bn_bwd_dx, dim3((unsigned)blocks), dim3(256), 0, stream, (const float4*)x, (const float4*)dy, (const float4*)y, mean,
-                       rstd, gamma, (const float*)dgamma, (const float*)dbeta, nvec, C / 4, 1.0f / (float)M, act, slope, (float4*)dx,
-                       (float4*)dres);
+    hipLaunchKernelGGL(k_bn_bwd_dx<false>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float4*)x, (const float4*)dy, (const float4*)y,
+                       mean, rstd, gamma, (const float*)dgamma, (const float*)dbeta, nvec, C / 4, 1.0f / (float)M, (const float*)nullptr, act,
+                       slope, (float4*)dx, (float4*)dres);
+    return far_check_launch();
+}
+
+// ---- SyncBatchNorm: K19 cut at the two points where the ranks exchange their sums.  No collective in here: the caller stacks the
+// records of all ranks as [W][K][C] float64 (K = 3 forward, 2 backward) in rank order and hands every rank the same bytes, so every
+// rank computes the same bits.  With W = 1 the five calls give the bits of far_bn_act_train_fwd_f32 / far_bn_train_bwd_f32.
+
+// rec: { n = M, sum x, sum x^2 }[C] float64 of this rank's x [M][C]; ws: far_bn_train_ws_bytes(M, C).
+int far_bn_sync_moments_f32(const float* x, long M, int C, double* rec, void* ws, long ws_bytes, hipStream_t stream) {
+    far_clear_errors();
+    if (!x || !rec || !ws || M <= 0 || C <= 0 || (C & 3) || C > 1024 || ws_bytes < far_bn_train_ws_bytes(M, C))
+        return FAR_EINVAL;
+    const int np = bn_parts(M);
+    const long per = (M + np - 1) / np;
+    hipLaunchKernelGGL(k_bn_partial<0>, dim3(np), dim3(BN_THREADS), 0, stream, (const float4*)x, (const float4*)nullptr,
+                       (const float4*)nullptr, (const float*)nullptr, (const float*)nullptr, M, C / 4, per, 0, 0.f, (float*)ws);
+    hipLaunchKernelGGL(k_bn_sync_moments, dim3((C + 63) / 64), dim3(BN_THREADS), 0, stream, (const float*)ws, np, M, per, C, rec);
+    return far_check_launch();
+}
+
+// recs: [W][3][C] float64.  vec: 4 C + 4 floats { scale[C], shift[C], mean[C], rstd[C], 1 / sum n, 0, 0, 0 }; running_mean /
+// running_var as far_bn_train_stats_f32 (the unbiased variance is over the total count).
+int far_bn_sync_stats_f32(const double* recs, int W, int C, const float* gamma, const float* beta, float eps, float momentum,
+                          float* running_mean, float* running_var, float* vec, hipStream_t stream) {
+    far_clear_errors();
+    if (!recs || !vec || W <= 0 || C <= 0 || (C & 3) || C > 1024)
+        return FAR_EINVAL;
+    hipLaunchKernelGGL(k_bn_sync_stats, dim3((C + 63) / 64), dim3(64), 0, stream, recs, W, C, gamma, beta, eps, momentum, running_mean,
+                       running_var, vec);
+    return far_check_launch();
+}
+
+// y = act(x scale + shift (+ res)) with vec from far_bn_sync_stats_f32 (k_bn_apply: the launch far_bn_act_train_fwd_f32 ends with).
+int far_bn_sync_apply_f32(const float* x, const float* res, long M, int C, const float* vec, int act, float slope, float* y,
+                          hipStream_t stream) {
+    far_clear_errors();
+    if (!x || !vec || !y || M <= 0 || C <= 0 || (C & 3) || C > 1024 || act < 0 || act > 2)
+        return FAR_EINVAL;
+    const long nvec = M * (C / 4);
+    long blocks = (nvec + 255) / 256;
+    blocks = blocks > 4096 ? 4096 : blocks;
+    hipLaunchKernelGGL(k_bn_apply, dim3((unsigned)blocks), dim3(256), 0, stream, (const float4*)x, vec, vec + C, (const float4*)res, nvec, C / 4,
+                       act, slope, (float4*)y);
+    return far_check_launch();
+}
+
+// rec: { sum g, sum g xhat }[C] float64 over this rank's pixels, g = dy act'(y), xhat from the GLOBAL mean / rstd in vec; dgamma /
+// dbeta: the same sums in fp32 -- this rank's weight / bias gradient (they stay per rank, as in torch's SyncBatchNorm).
+int far_bn_sync_bwd_sums_f32(const float* x, const float* dy, const float* y, const float* vec, long M, int C, int act, float slope,
+                             double* rec, float* dgamma, float* dbeta, void* ws, long ws_bytes, hipStream_t stream) {
+    far_clear_errors();
+    if (!x || !dy || !vec || !rec || !dgamma || !dbeta || !ws || M <= 0 || C <= 0 || (C & 3) || C > 1024 || act < 0 || act > 2 ||
+        (act && !y) || ws_bytes < far_bn_train_ws_bytes(M, C))
+        return FAR_EINVAL;
+    const int np = bn_parts(M);
+    const long per = (M + np - 1) / np;
+    hipLaunchKernelGGL(k_bn_partial<1>, dim3(np), dim3(BN_THREADS), 0, stream, (const float4*)x, (const float4*)dy, (const float4*)y,
+                       vec + 2 * C, vec + 3 * C, M, C / 4, per, act, slope, (float*)ws);
+    hipLaunchKernelGGL(k_bn_sync_bwd_sums, dim3((C + 63) / 64), dim3(BN_THREADS), 0, stream, (const float*)ws, np, C, rec, dgamma, dbeta);
+    return far_check_launch();
+}
+
+// recs: [W][2][C] float64.  dx = gamma rstd (g - S_g / Mt - xhat S_gx / Mt) with the sums over all ranks and Mt = sum n (1 / Mt from
+// vec); dres = g when dres != NULL.  sums: 2 C floats of scratch.  M: this rank's pixel count.
+int far_bn_sync_bwd_dx_f32(const float* x, const float* dy, const float* y, const float* vec, const float* gamma, const double* recs, int W,
+                           long M, int C, int act, float slope, float* dx, float* dres, float* sums, hipStream_t stream) {
+    far_clear_errors();
+    if (!x || !dy || !vec || !recs || !dx || !sums || W <= 0 || M <= 0 || C <= 0 || (C & 3) || C > 1024 || act < 0 || act > 2 || (act && !y))
+        return FAR_EINVAL;
+    hipLaunchKernelGGL(k_bn_sync_bwd_total, dim3((C + 63) / 64), dim3(64), 0, stream, recs, W, C, sums);
+    const long nvec = M * (C / 4);
+    long blocks = (nvec + 255) / 256;
+    blocks = blocks > 4096 ? 4096 : blocks;
+    hipLaunchKernelGGL(k_bn_bwd_dx<true>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float4*)x, (const float4*)dy, (const float4*)y,
+                       vec + 2 * C, vec + 3 * C, gamma, (const float*)(sums + C), (const float*)sums, nvec, C / 4, 0.f, vec + 4 * C, act, slope,
+                       (float4*)dx, (float4*)dres);
     return far_check_launch();
 }
 

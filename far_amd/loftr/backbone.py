@@ -77,10 +77,12 @@ def _c3(i, o, s=1):
 
 
 def _bn_hip(bn, x):
-    """BatchNorm with batch statistics on K19: a plain nn.BatchNorm2d in training mode (NOT SyncBatchNorm -- the reference's multi-GPU
-    training converts the modules, train.py:342: their statistics span the ranks and stay with torch), fp32 GPU tensor, gradients
-    enabled."""
-    return (ResNetFPN_8_2.hip_training and ops.USE_HIP_BATCHNORM_TRAIN and type(bn) is nn.BatchNorm2d and bn.training and x.is_cuda
+    """BatchNorm with batch statistics on K19: a plain nn.BatchNorm2d in training mode, fp32 GPU tensor, gradients enabled.  The
+    reference's multi-GPU training converts the modules to SyncBatchNorm (train.py:342: their statistics span the ranks): those stay
+    with torch unless ops.USE_HIP_SYNC_BATCHNORM is on (LoFTR.set_sync_batchnorm_training), then they run K19's synchronised form.
+    Nothing rank-local enters the decision: the ranks must agree on who calls the collective."""
+    return (ResNetFPN_8_2.hip_training and ops.USE_HIP_BATCHNORM_TRAIN
+            and (type(bn) is nn.BatchNorm2d or (ops.USE_HIP_SYNC_BATCHNORM and type(bn) is nn.SyncBatchNorm)) and bn.training and x.is_cuda
             and x.dtype == torch.float32 and torch.is_grad_enabled())
 
 

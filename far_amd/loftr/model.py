@@ -176,6 +176,15 @@ class LoFTR(nn.Module):
                 m.full_training = m.attention.full_training = bool(on)
         return self
 
+    def set_sync_batchnorm_training(self, on=True):
+        """Training with the backbone converted by torch.nn.SyncBatchNorm.convert_sync_batchnorm (mp3d_loftr/train.py:342): the converted
+        layers run K19's synchronised form (ops.bn_act_train: HIP statistics over all ranks, one all_reduce forward and one backward,
+        fused activation / shortcut add, fixed-order backward) instead of torch's SyncBatchNorm.  The switch is ops.USE_HIP_SYNC_BATCHNORM:
+        process-wide (a rank is a process) and it must be set alike on every rank, before or after the conversion.  Off by default;
+        inference and plain BatchNorm2d models are unchanged either way."""
+        ops.USE_HIP_SYNC_BATCHNORM = bool(on)
+        return self
+
     # -------------------------------------------------------------------------------------------------
     # stage 1: local feature CNN on both images at once (loftr.py:56-89)
     # -------------------------------------------------------------------------------------------------

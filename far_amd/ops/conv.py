@@ -184,18 +184,170 @@ class _BatchNormActFn(torch.autograd.Function):
 
 USE_HIP_BATCHNORM_TRAIN = not flags.off('FAR_NO_BN')      # False: nn.BatchNorm2d + torch activations under autograd (comparison leg, --vendor-train)
 
-def bn_act_train(x, bn, act='none', slope=0.01, residual=None):
+USE_HIP_SYNC_BATCHNORM = False       # True: torch.nn.SyncBatchNorm modules in training mode run K19's synchronised form (opt-in:
+                                     # LoFTR.set_sync_batchnorm_training; process-wide, and it must be set alike on every rank)
+
+def _cl(t):
+    """(N, C, H, W) fp32 GPU tensor in channels_last memory, as [M][C] for the K19 entry points."""
+    if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4:
+        raise _lib.FarHipError('the BatchNorm kernels need fp32 GPU (N, C, H, W) tensors')
+    t = t.detach().contiguous(memory_format=torch.channels_last)
+    if t.numel() == 0:
+        raise _lib.FarHipError('the synchronised BatchNorm kernels need at least one pixel on every rank')
+    return t
+
+def _ws_f32(nbytes, device):
+    """K19's partial-sum scratch (far_bn_train_ws_bytes: a multiple of four bytes)."""
+    return torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=device)
+
+def sync_bn_moments(x, out=None):
+    """K19, synchronised form, stage 1 (no collective): this rank's record { n, sum x, sum x^2 } as a (3, C) float64 tensor (`out`: a
+    contiguous (3, C) float64 slot to write it into, e.g. row `rank` of the (W, 3, C) exchange buffer)."""
+    lib = _lib.load()
+    xc = _cl(x)
+    N, C, H, W = xc.shape
+    M = N * H * W
+    rec = torch.empty(3, C, dtype=torch.float64, device=xc.device) if out is None else out
+    nb = int(lib.far_bn_train_ws_bytes(M, C))
+    ws = _ws_f32(nb, xc.device)
+    _lib.check(lib.far_bn_sync_moments_f32(xc.data_ptr(), M, C, _p(rec, torch.float64), ws.data_ptr(), nb, _stream()), 'far_bn_sync_moments_f32')
+    return rec if out is None else _written(rec)
+
+def sync_bn_stats(recs, weight=None, bias=None, eps=1e-5, momentum=0.1, running_mean=None, running_var=None):
+    """Stage 2 (no collective): the stacked records (W, 3, C) float64 of all ranks, added in rank order -> a float32 vector of 4 C + 4
+    entries { scale, shift, mean, rstd, 1 / total count }; running_mean / running_var are updated in place as the module does
+    (momentum, unbiased variance over the total count).  Every rank that passes the same bytes gets the same bits."""
+    lib = _lib.load()
+    if recs.dim() != 3 or recs.shape[1] != 3:
+        raise _lib.FarHipError('sync_bn_stats expects the records as a (W, 3, C) float64 tensor')
+    W, _, C = recs.shape
+    vec = torch.empty(4 * C + 4, dtype=torch.float32, device=recs.device)
+    rc = lib.far_bn_sync_stats_f32(_p(recs, torch.float64), W, C, _p(weight, torch.float32), _p(bias, torch.float32), float(eps), float(momentum),
+                                   _p(running_mean, torch.float32), _p(running_var, torch.float32), _p(vec), _stream())
+    _lib.check(rc, 'far_bn_sync_stats_f32')
+    _written(running_mean)
+    _written(running_var)
+    return vec
+
+def sync_bn_apply(x, vec, act='none', slope=0.01, residual=None):
+    """Stage 3: y = act(x scale + shift (+ residual)) with the vector of sync_bn_stats; channels_last memory."""
+    lib = _lib.load()
+    xc = _cl(x)
+    N, C, H, W = xc.shape
+    r = None if residual is None else _cl(residual)
+    if vec.numel() != 4 * C + 4 or (r is not None and r.shape != xc.shape):
+        raise _lib.FarHipError('sync_bn_apply: the statistics vector or the residual does not fit x')
+    y = torch.empty_like(xc)
+    rc = lib.far_bn_sync_apply_f32(xc.data_ptr(), 0 if r is None else r.data_ptr(), N * H * W, C, _p(vec, torch.float32), _ACT[act], float(slope),
+                                   y.data_ptr(), _stream())
+    _lib.check(rc, 'far_bn_sync_apply_f32')
+    return y
+
+def sync_bn_bwd_sums(x, dy, y, vec, act='none', slope=0.01, out=None):
+    """Backward stage 1 (no collective): this rank's record { sum g, sum g xhat } as (2, C) float64 (g = dy act'(y), xhat from the global
+    statistics in vec), and the same sums in fp32 as this rank's (dgamma, dbeta).  Returns (rec, dgamma, dbeta)."""
+    lib = _lib.load()
+    xc, gc, yc = _cl(x), _cl(dy), _cl(y)
+    N, C, H, W = xc.shape
+    M = N * H * W
+    if vec.numel() != 4 * C + 4 or gc.shape != xc.shape or yc.shape != xc.shape:
+        raise _lib.FarHipError('sync_bn_bwd_sums: the statistics vector, dy or y does not fit x')
+    rec = torch.empty(2, C, dtype=torch.float64, device=xc.device) if out is None else out
+    dgb = torch.empty(2, C, dtype=torch.float32, device=xc.device)
+    nb = int(lib.far_bn_train_ws_bytes(M, C))
+    ws = _ws_f32(nb, xc.device)
+    rc = lib.far_bn_sync_bwd_sums_f32(xc.data_ptr(), gc.data_ptr(), yc.data_ptr(), _p(vec, torch.float32), M, C, _ACT[act], float(slope),
+                                      _p(rec, torch.float64), dgb.data_ptr(), dgb.data_ptr() + 4 * C, ws.data_ptr(), nb, _stream())
+    _lib.check(rc, 'far_bn_sync_bwd_sums_f32')
+    return (rec if out is None else _written(rec)), dgb[0], dgb[1]
+
+def sync_bn_bwd_dx(x, dy, y, vec, weight, recs, act='none', slope=0.01, want_dres=False):
+    """Backward stage 2: the stacked records (W, 2, C) float64, added in rank order -> dx = gamma rstd (g - S_g / M - xhat S_gx / M) with
+    the global sums and the global count; returns (dx, dres) with dres = g when want_dres, else None."""
+    lib = _lib.load()
+    xc, gc, yc = _cl(x), _cl(dy), _cl(y)
+    N, C, H, W = xc.shape
+    if recs.dim() != 3 or tuple(recs.shape[1:]) != (2, C) or vec.numel() != 4 * C + 4 or gc.shape != xc.shape or yc.shape != xc.shape:
+        raise _lib.FarHipError('sync_bn_bwd_dx: the records, the statistics vector, dy or y do not fit x')
+    dx = torch.empty_like(xc)
+    dres = torch.empty_like(xc) if want_dres else None
+    sums = torch.empty(2 * C, dtype=torch.float32, device=xc.device)
+    rc = lib.far_bn_sync_bwd_dx_f32(xc.data_ptr(), gc.data_ptr(), yc.data_ptr(), _p(vec, torch.float32), _p(weight, torch.float32),
+                                    _p(recs, torch.float64), recs.shape[0], N * H * W, C, _ACT[act], float(slope), dx.data_ptr(),
+                                    0 if dres is None else dres.data_ptr(), sums.data_ptr(), _stream())
+    _lib.check(rc, 'far_bn_sync_bwd_dx_f32')
+    return dx, dres
+
+def _exchange(rec_fn, K, C, device, group, world, rank):
+    """Every rank's (K, C) float64 record on every rank, as (W, K, C): each rank writes its record into its own slot of a zeroed
+    buffer, one all_reduce(SUM) adds the buffers -- adding zeros is exact, so every record arrives unchanged whatever order the
+    backend reduces in (RCCL and gloo alike)."""
+    buf = torch.zeros(world, K, C, dtype=torch.float64, device=device)
+    out = rec_fn(buf[rank])
+    torch.distributed.all_reduce(buf, op=torch.distributed.ReduceOp.SUM, group=group)
+    return buf, out
+
+class _SyncBatchNormActFn(torch.autograd.Function):
+    """act(bn(x) (+ residual)) for a torch.nn.SyncBatchNorm in training mode (mp3d_loftr/train.py:342): K19's synchronised form -- the five
+    sync_bn_* stages with one all_reduce in the forward ({ n, sum x, sum x^2 } of every rank) and one in the backward ({ sum g,
+    sum g xhat }).  dgamma / dbeta stay per rank (DistributedDataParallel averages them), as with torch's module."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, bn, act, slope, residual, group, world, rank):
+        xc = _cl(x)
+        C = xc.shape[1]
+        track = bn.track_running_stats and bn.running_mean is not None
+        recs, _ = _exchange(lambda slot: sync_bn_moments(xc, out=slot), 3, C, xc.device, group, world, rank)
+        vec = sync_bn_stats(recs, weight, bias, bn.eps, bn.momentum, bn.running_mean if track else None, bn.running_var if track else None)
+        y = sync_bn_apply(xc, vec, act, slope, residual)
+        if track:
+            bn.num_batches_tracked += 1
+        ctx.save_for_backward(xc, y, vec, weight)
+        ctx.act, ctx.slope, ctx.has_res, ctx.pg = act, float(slope), residual is not None, (group, world, rank)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        xc, y, vec, weight = ctx.saved_tensors
+        C = xc.shape[1]
+        gc = g.contiguous(memory_format=torch.channels_last)
+        recs, (_, dgamma, dbeta) = _exchange(lambda slot: sync_bn_bwd_sums(xc, gc, y, vec, ctx.act, ctx.slope, out=slot), 2, C, xc.device, *ctx.pg)
+        dx, dres = sync_bn_bwd_dx(xc, gc, y, vec, weight, recs, ctx.act, ctx.slope, want_dres=ctx.has_res)
+        return (dx, dgamma if weight is not None else None, dbeta if weight is not None else None, None, None, None, dres, None, None, None)
+
+def _sync_group(bn):
+    """(process group, world size, rank) of a SyncBatchNorm module; (None, 1, 0) without an initialised process group."""
+    dist = torch.distributed
+    if not (dist.is_available() and dist.is_initialized()):
+        return None, 1, 0
+    group = bn.process_group if bn.process_group is not None else dist.group.WORLD
+    return group, dist.get_world_size(group), dist.get_rank(group)
+
+def bn_act_train(x, bn, act='none', slope=0.01, residual=None, force_exchange=False):
     """K19.  act(bn(x) (+ residual)) for an nn.BatchNorm2d in TRAINING mode (batch statistics) on a GPU tensor, with gradients;
-    what the kernels do not cover (eval-mode modules, momentum None, C % 4 != 0, C > 1024) runs the module and torch activations."""
+    what the kernels do not cover (eval-mode modules, momentum None, C % 4 != 0, C > 1024) runs the module and torch activations.
+    With USE_HIP_SYNC_BATCHNORM a torch.nn.SyncBatchNorm takes the synchronised form: statistics over all ranks of the module's
+    process_group, one all_reduce forward and one backward; at world size 1 (or without a process group) no collective is issued
+    and the call is the plain one, as with torch's module.  Whether such a module runs here depends only on what is equal on every
+    rank (the switch, the module's configuration, C, dtype): a rank-local obstacle (an empty shard) raises instead of leaving the
+    other ranks alone in the collective.  force_exchange: run the exchange at world size 1 too (a test aid)."""
     if not x.is_cuda:
         raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
     C = x.shape[1]
-    if (not USE_HIP_BATCHNORM_TRAIN or type(bn) is not torch.nn.BatchNorm2d or not bn.training or bn.momentum is None or (C & 3) or C > 1024 or x.dtype != torch.float32
-            or x.numel() == 0 or (bn.weight is None) != (bn.bias is None)):
+    sync = USE_HIP_SYNC_BATCHNORM and type(bn) is torch.nn.SyncBatchNorm
+    if (not USE_HIP_BATCHNORM_TRAIN or not (type(bn) is torch.nn.BatchNorm2d or sync) or not bn.training or bn.momentum is None or (C & 3) or C > 1024
+            or x.dtype != torch.float32 or x.dim() != 4 or (x.numel() == 0 and not sync) or (bn.weight is None) != (bn.bias is None)):
         y = bn(x)
         if residual is not None:
             y = y + residual
         return torch.relu(y) if act == 'relu' else (torch.nn.functional.leaky_relu(y, slope) if act == 'leaky' else y)
+    if sync:
+        if x.numel() == 0:
+            raise _lib.FarHipError('SyncBatchNorm on the HIP kernels needs at least one pixel on every rank (an empty shard cannot fall '
+                                   'back to the module: the other ranks are already in the collective)')
+        group, world, rank = _sync_group(bn)
+        if world > 1 or (force_exchange and group is not None):
+            return _SyncBatchNormActFn.apply(x, bn.weight, bn.bias, bn, act, slope, residual, group, world, rank)
     return _BatchNormActFn.apply(x, bn.weight, bn.bias, bn, act, slope, residual)
 
 class _Upsample2xAddFn(torch.autograd.Function):

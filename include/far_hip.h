@@ -30,7 +30,7 @@ typedef struct ihipStream_t* far_stream_t; /* == hipStream_t */
 
 /* ABI version of this header; bumped when a signature changes (2: activation exponent / overflow flag of K9, K13, K14; 3: the
  * far_wino_* / far_conv3x3_wino_f32 entry points, 16 tuning keys; 4: far_upsample2x_bwd_f32, far_fine_scatter_det_f32, far_bn_train_*, far_adamw_*; 5: far_linear_kv_f16s, far_linear_q_apply_f16s,
- * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way, and so were far_grad_norm_workspace_bytes, far_grad_norm_f32, far_grad_clip_scale_f32 and far_adam_step_f32).  far_amd/_lib.py refuses a library whose version differs. */
+ * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way, and so were far_grad_norm_workspace_bytes, far_grad_norm_f32, far_grad_clip_scale_f32 and far_adam_step_f32, and the five far_bn_sync_*_f32 entry points).  far_amd/_lib.py refuses a library whose version differs. */
 int far_abi_version(void);
 /* Id of the sources the library was built from: sha256/16 over far_amd/csrc/* and the compiler flags (far_amd/build.py
  * source_id()).  far_amd/_lib.py refuses a library whose id differs from the sources it sits next to. */
@@ -514,6 +514,31 @@ int far_bn_train_stats_f32(const float* x, long M, int C, const float* gamma, co
 int far_bn_train_bwd_f32(const float* x, const float* dy, const float* y, const float* mean, const float* rstd, const float* gamma,
                          long M, int C, int act, float slope, float* dx, float* dgamma, float* dbeta, float* dres, void* ws,
                          long ws_bytes, far_stream_t stream);
+
+/* K19 for torch.nn.SyncBatchNorm (mp3d_loftr/train.py:342 converts all 17 BatchNorm2d layers; the statistics span the ranks): the
+ * same arithmetic cut at the two points where the ranks meet.  The library issues no collective: the caller stacks the float64
+ * records of all W ranks in rank order ([W][3][C] forward, [W][2][C] backward; far_amd.ops does it with one all-reduce of a zeroed
+ * buffer in which each rank filled its own slot) and every rank passes the same bytes, so every rank computes the same bits.  With
+ * W = 1 the five calls give the bits of far_bn_act_train_fwd_f32 / far_bn_train_bwd_f32.  Same shapes: C % 4 == 0, C <= 1024.
+ *   far_bn_sync_moments_f32: rec = { n = M, sum x, sum x^2 }[C] of this rank's x [M][C]; ws: far_bn_train_ws_bytes(M, C).
+ *   far_bn_sync_stats_f32: the records added in rank order, then far_bn_train_stats_f32's expressions with M = sum n.  vec: 4 C + 4
+ *     floats { scale[C], shift[C], mean[C], rstd[C], 1 / sum n, 0, 0, 0 }; running_mean / running_var updated in place (unbiased
+ *     variance over the total count), either may be NULL.
+ *   far_bn_sync_apply_f32: y = act(x scale + shift (+ res)) with that vec.
+ *   far_bn_sync_bwd_sums_f32: rec = { sum g, sum g xhat }[C] over this rank's pixels (g = dy act'(y), xhat from the global mean /
+ *     rstd in vec); dgamma / dbeta: the same sums in fp32 -- this rank's weight / bias gradient, as torch's SyncBatchNorm leaves
+ *     them per rank.
+ *   far_bn_sync_bwd_dx_f32: the records added in rank order, dx = gamma rstd (g - S_g / Mt - xhat S_gx / Mt) with Mt = sum n (read
+ *     from vec), dres = g when dres != NULL.  M: this rank's pixel count; sums: 2 C floats of scratch. */
+int far_bn_sync_moments_f32(const float* x, long M, int C, double* rec, void* ws, long ws_bytes, far_stream_t stream);
+int far_bn_sync_stats_f32(const double* recs, int W, int C, const float* gamma, const float* beta, float eps, float momentum,
+                          float* running_mean, float* running_var, float* vec, far_stream_t stream);
+int far_bn_sync_apply_f32(const float* x, const float* res, long M, int C, const float* vec, int act, float slope, float* y,
+                          far_stream_t stream);
+int far_bn_sync_bwd_sums_f32(const float* x, const float* dy, const float* y, const float* vec, long M, int C, int act, float slope,
+                             double* rec, float* dgamma, float* dbeta, void* ws, long ws_bytes, far_stream_t stream);
+int far_bn_sync_bwd_dx_f32(const float* x, const float* dy, const float* y, const float* vec, const float* gamma, const double* recs, int W,
+                           long M, int C, int act, float slope, float* dx, float* dres, float* sums, far_stream_t stream);
 
 /* Gradient of that upsampling with respect to lo: dlo [N][h][w][C] from dout [N][2h][2w][C] (channels_last memory, C % 4 == 0),
  * gathered in a fixed order -- bit-identical from run to run.  Replaces the autograd node torch records for
