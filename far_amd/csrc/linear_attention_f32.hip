@@ -305,7 +305,7 @@ size_t far_linear_attention_workspace_bytes(int N, int S, int H, int D) {
     return ((size_t)N * nchunk + N) * (size_t)H * D * (D + 1) * sizeof(float);
 }
 
-// out [N][L][H*D] = LinearAttention(q [N][L][H*D], k, v [N][S][H*D]); D in {16, 32}; H*D in {128, 256}.
+// out [N][L][H*D] = LinearAttention(q [N][L][H*D], k, v [N][S][H*D]); D in {16, 32}; H*D <= 1024 (LoFTR: 128, 256).
 int far_linear_attention_f32(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D,
                              const uint8_t* q_mask, const uint8_t* kv_mask, float eps, float* out, void* ws,
                              hipStream_t stream) {
@@ -313,7 +313,7 @@ int far_linear_attention_f32(const float* q, const float* k, const float* v, int
     if (N == 0) return FAR_OK;
     if (!q || !k || !v || !out || !ws || N < 0 || L <= 0 || S <= 0) return FAR_EINVAL;
     const int HD = H * D;
-    if (HD > 1024 || (HD % 64) != 0) return FAR_EINVAL;
+    if (H <= 0 || HD > 1024) return FAR_EINVAL;             // any head count: a wave works on one head, rows are H * D floats (16-byte groups)
     if (D == 32) return launch_la<32>(q, k, v, N, L, S, H, q_mask, kv_mask, eps, out, (float*)ws, stream);
     if (D == 16) return launch_la<16>(q, k, v, N, L, S, H, q_mask, kv_mask, eps, out, (float*)ws, stream);
     return FAR_EINVAL;
@@ -546,7 +546,7 @@ int far_linear_attention_bwd_f32(const float* q, const float* k, const float* v,
     if (N == 0) return FAR_OK;
     if (!q || !k || !v || !g || !dq || !dk || !dv || !ws || N < 0 || L <= 0 || S <= 0) return FAR_EINVAL;
     const int HD = H * D;
-    if (HD > 1024 || (HD % 64) != 0) return FAR_EINVAL;
+    if (H <= 0 || HD > 1024) return FAR_EINVAL;             // any head count: a wave works on one head, rows are H * D floats (16-byte groups)
     if (D == 32) return launch_la_bwd<32>(q, k, v, g, N, L, S, H, q_mask, kv_mask, eps, dq, dk, dv, (float*)ws, stream);
     if (D == 16) return launch_la_bwd<16>(q, k, v, g, N, L, S, H, q_mask, kv_mask, eps, dq, dk, dv, (float*)ws, stream);
     return FAR_EINVAL;
