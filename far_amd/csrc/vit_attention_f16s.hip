@@ -1,0 +1,347 @@
+// K23: the softmax self-attention core of the 8-Point-ViT's Blocks (head dim 64) on the f16 matrix cores with split-precision operands.
+//
+// Operator (reference: interiornetStreetlearn_8ptVit/src/modules/vision_transformer.py:250-258, inference, no dropout, no masks):
+//   out[n, l, h, :] = sum_s softmax_s(q[n,l,h,:] . k[n,s,h,:] / sqrt(64)) v[n,s,h,:]
+// A new translation unit on K22's recipe (full_attention_f16s.hip: read its header first); K22 itself stays a 32-channel kernel
+// (one 32 x 32 output block per wave, a 32-row v^T plane) and keeps refusing head dim 64.  What differs here:
+//   layout   q, k, v are addressed by (image, head, row) strides, rows of 64 contiguous floats: the head planes (3h, Z, N, 64) that
+//            the qkv Linear writes with out_planes = 3h (the layout K2 reads in place) and the concatenated (Z, N, h 64) form are
+//            the same code.  out is (Z, L, h 64) with the heads concatenated: what the `proj` Linear reads.
+//   scores   the contraction runs over 64 channels: four 32x32x16 k-steps per 32 keys (x 3 for hi.hi + hi.lo + lo.hi).
+//   P V      two 32-wide output blocks per query row: every p fragment multiplies v^T rows d and d + 32 (two accumulator blocks).
+//   stage    k as [key][64] rows, v^T as [64][keys] rows, hi and lo planes: 4 x 8 KB = 32 KB per 64-key tile, two stages = 64 KB,
+//            two workgroups per CU.  Both kinds of row are 128 bytes: slot c of row r sits at c ^ ((r >> 1) & 7), so the 16 rows a
+//            ds_read_b128 lane group reads cover the 256-byte bank row exactly once.
+//   keys     no masks: a key takes part when its index is below S.  Keys past S are written as zeros and SELECTED to p = 0 (never
+//            exp'ed into the sum); the validity of a tile is arithmetic, no mask word in LDS.
+// As in K22: one workgroup = 128 query rows of one (image, head), 32 per wave; the next tile's fp32 loads are in flight while this
+// one is computed; online softmax in the log2 domain with the INTEGER row reference R = ceil(running maximum), so a rescale is an
+// exact power of two; p = 2^(x - R + 15); the tile's row-sum terms are added with Kahan compensation; out = acc / rowsum 2^-act_exp.
+// The (L, S) scores never reach memory, there is no workspace, no float atomics, and the launch geometry depends on (L, H) and the
+// image index only: an image's output bits do not depend on the batch.  The key axis is not split (K22 does for short L).
+// Range: |x| 2^act_exp <= 65504 for every q / k / v value that takes part; a launch that sees a value beyond it (or a non-finite
+// one) ORs the overflow flag, like every split-fp16 kernel of this library.
+#include "common.h"
+#include <type_traits>
+
+namespace {
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+constexpr float NEG_HUGE = -1.0e30f;
+constexpr int ROW_REF0 = -(1 << 24);     // row reference before the first tile
+constexpr int P_EXP = 15;                // p is formed as 2^(x - R + 15): its fp16 lo part stays normal down to p = 2^-18 max
+
+constexpr int D = 64;                    // head dim
+constexpr int KT = 64, NCT = KT / 32;    // keys per tile, 32-key score blocks per tile
+constexpr int WAVES = 4, NT = 64 * WAVES, ROWS = 32 * WAVES;
+constexpr int QS = D / 16;               // k-steps of the score contraction
+constexpr int NOB = D / 32;              // 32-wide output blocks
+constexpr int PLANE = KT * D * 2;        // bytes of one plane (k hi, k lo, v^T hi, v^T lo): 8 KB
+constexpr int STAGE = 4 * PLANE;         // 32 KB
+constexpr int KCH = KT * (D / 8) / NT;   // k chunks (8 channels of one key) per thread: 2
+constexpr int VCH = D * (KT / 8) / NT;   // v^T items (8 keys of one channel) per thread: 2
+static_assert(KT * (D / 8) % NT == 0 && D * (KT / 8) % NT == 0, "staging items divide over the threads");
+
+// 16-byte slot c of the 128-byte row `row` (a key's 64 channels, or a channel's 64 keys)
+__device__ __forceinline__ int row_off(int row, int c) { return row * 128 + ((c ^ ((row >> 1) & 7)) * 16); }
+
+struct Args {
+    const float *q, *k, *v;
+    float* out;
+    int* overflow;
+    long q_img, q_head, q_row, kv_img, kv_head, kv_row;     // strides in floats
+    int Z, L, S, H, nI;
+    float pre, c1, out_mul;
+};
+
+__device__ __forceinline__ void split8(const float (&x)[8], float pre, f16x8& hi, f16x8& lo) {
+#pragma unroll
+    for (int e = 0; e < 8; e += 2) {
+        f16x2 h2, l2;
+        split2(f32x2{x[e], x[e + 1]} * f32x2{pre, pre}, h2, l2);
+        hi[e] = h2.x; hi[e + 1] = h2.y;
+        lo[e] = l2.x; lo[e + 1] = l2.y;
+    }
+}
+
+__device__ __forceinline__ bool out_of_range(const float (&x)[8], float pre) {
+    bool bad = false;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) bad |= !(fabsf(x[e]) * pre <= 65504.0f);
+    return bad;
+}
+
+// One key tile on its way from global memory to LDS: fp32 in registers while the previous tile is computed.
+struct Staged {
+    float kx[KCH][8];
+    float vx[VCH][8];
+
+    __device__ __forceinline__ void load(const Args& a, const float* kb, const float* vb, int jt, int tid) {
+        const int j0 = jt * KT;
+#pragma unroll
+        for (int ci = 0; ci < KCH; ++ci) {
+            const int c = tid + ci * NT;
+            const int key = c >> 3, sl = c & 7;
+            const int j = j0 + key;
+            float4 u = make_float4(0.f, 0.f, 0.f, 0.f), w = u;
+            if (j < a.S) {
+                const float* p = kb + (size_t)j * a.kv_row + sl * 8;
+                u = *reinterpret_cast<const float4*>(p);
+                w = *reinterpret_cast<const float4*>(p + 4);
+            }
+            kx[ci][0] = u.x; kx[ci][1] = u.y; kx[ci][2] = u.z; kx[ci][3] = u.w;
+            kx[ci][4] = w.x; kx[ci][5] = w.y; kx[ci][6] = w.z; kx[ci][7] = w.w;
+        }
+#pragma unroll
+        for (int ci = 0; ci < VCH; ++ci) {
+            const int c = tid + ci * NT;
+            const int d = c & 63, g = c >> 6;                       // g = 4 ct + 2 u + h: the slot of MFMA (ct, u), half-wave h
+            // position e of the slot holds key 32 ct + 16 u + 4 h + (e < 4 ? e : e + 4): accumulator registers 8 u .. 8 u + 7
+            const int kbase = 32 * (g >> 2) + 16 * ((g >> 1) & 1) + 4 * (g & 1);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const int j = j0 + kbase + (e < 4 ? e : e + 4);
+                vx[ci][e] = j < a.S ? vb[(size_t)j * a.kv_row + d] : 0.f;
+            }
+        }
+    }
+
+    // -> true when a staged value is beyond the split's range (checked by the workgroups of row block 0 only: `check`)
+    __device__ __forceinline__ bool store(unsigned char* st, float pre, int tid, bool check) {
+        bool bad = false;
+#pragma unroll
+        for (int ci = 0; ci < KCH; ++ci) {
+            const int c = tid + ci * NT;
+            f16x8 hi, lo;
+            split8(kx[ci], pre, hi, lo);
+            if (check) bad |= out_of_range(kx[ci], pre);
+            const int off = row_off(c >> 3, c & 7);
+            *reinterpret_cast<f16x8*>(st + off) = hi;
+            *reinterpret_cast<f16x8*>(st + PLANE + off) = lo;
+        }
+#pragma unroll
+        for (int ci = 0; ci < VCH; ++ci) {
+            const int c = tid + ci * NT;
+            f16x8 hi, lo;
+            split8(vx[ci], pre, hi, lo);
+            if (check) bad |= out_of_range(vx[ci], pre);
+            const int off = row_off(c & 63, c >> 6);
+            *reinterpret_cast<f16x8*>(st + 2 * PLANE + off) = hi;
+            *reinterpret_cast<f16x8*>(st + 3 * PLANE + off) = lo;
+        }
+        return bad;
+    }
+};
+
+__global__ __launch_bounds__(NT, 2) void k_vit_attention(Args a) {
+    __shared__ __attribute__((aligned(16))) unsigned char lds_all[2 * STAGE];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
+    // block -> (image-head z, row block Ib): the row blocks of one z share an XCD's L2 (common.h: tile_coords)
+    const int ZH = a.Z * a.H;
+    const int id = blockIdx.x;
+    int z, Ib;
+    if ((ZH & 7) == 0) {
+        const int xcd = id & 7, li = id >> 3;
+        z = xcd + 8 * (li / a.nI);
+        Ib = li % a.nI;
+    } else {
+        z = id / a.nI;
+        Ib = id - z * a.nI;
+    }
+    const int n = z / a.H, hh = z - n * a.H;
+    const int i0 = Ib * ROWS + 32 * wave;
+    const int irow = i0 + l31;
+    const bool qok = irow < a.L;
+    bool bad = false;
+
+    // ---- this lane's query row: channels 16 s + 8 h .. + 7 of both planes (the B operand of the score MFMAs)
+    f16x8 qh[QS], ql[QS];
+#pragma unroll
+    for (int s = 0; s < QS; ++s) {
+        float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (qok) {
+            const float* p = a.q + (size_t)n * a.q_img + (size_t)hh * a.q_head + (size_t)irow * a.q_row + 16 * s + 8 * h;
+            const float4 u = *reinterpret_cast<const float4*>(p);
+            const float4 w = *reinterpret_cast<const float4*>(p + 4);
+            x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w; x[4] = w.x; x[5] = w.y; x[6] = w.z; x[7] = w.w;
+        }
+        bad |= out_of_range(x, a.pre);
+        split8(x, a.pre, qh[s], ql[s]);
+    }
+
+    f32x16 tacc[NOB];
+#pragma unroll
+    for (int ob = 0; ob < NOB; ++ob)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) tacc[ob][r] = 0.f;
+    int R = ROW_REF0;                      // integer row reference, equal in lanes l and l + 32
+    float sum = 0.f, comp = 0.f;           // this half-wave's share of the row sum (Kahan-compensated per tile)
+
+    const float* const kb = a.k + (size_t)n * a.kv_img + (size_t)hh * a.kv_head;
+    const float* const vb = a.v + (size_t)n * a.kv_img + (size_t)hh * a.kv_head;
+    const int ntile = (a.S + KT - 1) / KT;
+    const bool check = Ib == 0;
+    Staged st;
+    st.load(a, kb, vb, 0, tid);
+    bad |= st.store(lds_all, a.pre, tid, check);
+    __syncthreads();
+    for (int jt = 0; jt < ntile; ++jt) {
+        // tile jt is in stage jt & 1; the other stage was last read before the barrier that ended the previous iteration:
+        // tile jt + 1 goes there once its loads (issued now, in flight during the MFMAs) have arrived
+        const unsigned char* const lds = lds_all + (jt & 1) * STAGE;
+        const unsigned char* const ldv = lds + 2 * PLANE;
+        const bool more = jt + 1 < ntile;
+        if (more) st.load(a, kb, vb, jt + 1, tid);
+
+        f32x16 acc[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
+#pragma unroll
+        for (int s = 0; s < QS; ++s) {
+            f16x8 ch[NCT], cl[NCT];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                const int off = row_off(32 * ct + l31, 2 * s + h);
+                ch[ct] = *reinterpret_cast<const f16x8*>(lds + off);
+                cl[ct] = *reinterpret_cast<const f16x8*>(lds + PLANE + off);
+            }
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], qh[s], acc[ct], 0, 0, 0);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], ql[s], acc[ct], 0, 0, 0);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[ct], qh[s], acc[ct], 0, 0, 0);
+        }
+        // validity of this lane's keys: accumulator register r of score block ct is key 32 ct + mfma32_row(r, h) of the tile
+        const int nvalid = a.S - jt * KT;                                                  // >= 1
+        const bool ragged = nvalid < KT;                                                   // workgroup-uniform: the last tile only
+        auto key_ok = [&](int ct, int r) { return 32 * ct + mfma32_row(r, h) < nvalid; };
+
+        // ---- row reference: ceil of the running maximum (log2 domain), agreed between the two half-waves
+        float tm = NEG_HUGE;
+        if (ragged) {
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tm = fmaxf(tm, key_ok(ct, r) ? acc[ct][r] : NEG_HUGE);
+        } else {
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tm = fmaxf(tm, acc[ct][r]);
+        }
+        tm *= a.c1;                                                                        // c1 > 0
+        int Rn = (int)ceilf(fminf(fmaxf(tm, -1.0e6f), 1.0e6f));
+        Rn = Rn > R ? Rn : R;
+        const int Ro = __shfl_xor(Rn, 32, 64);
+        Rn = Rn > Ro ? Rn : Ro;
+        if (__any(Rn != R)) {                                                              // rare after the first tiles
+            int d = R - Rn;                                                                // <= 0
+            d = d < -200 ? -200 : d;                                                       // 2^-200 flushes every fp32 to zero already
+            sum = ldexpf(sum, d);
+            comp = ldexpf(comp, d);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {                                                 // register r: query mfma32_row(r, h)
+                const int dr = __shfl(d, mfma32_row(r, h), 64);
+#pragma unroll
+                for (int ob = 0; ob < NOB; ++ob) tacc[ob][r] = ldexpf(tacc[ob][r], dr);
+            }
+            R = Rn;
+        }
+        const float nR = (float)(P_EXP - R);
+        float t = 0.f;
+        auto pv_tile = [&](auto ragged_c) {
+            constexpr bool RAGGED = decltype(ragged_c)::value;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    float p[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const int r = 8 * u + e;
+                        p[e] = __builtin_amdgcn_exp2f(fmaf(acc[ct][r], a.c1, nR));
+                        if (RAGGED) p[e] = key_ok(ct, r) ? p[e] : 0.f;                     // selected out, whatever the score was
+                        t += p[e];
+                    }
+                    f16x8 ph, pl;
+                    split8(p, 1.0f, ph, pl);
+#pragma unroll
+                    for (int ob = 0; ob < NOB; ++ob) {
+                        const int off = row_off(32 * ob + l31, 4 * ct + 2 * u + h);
+                        const f16x8 bh = *reinterpret_cast<const f16x8*>(ldv + off);
+                        const f16x8 bl = *reinterpret_cast<const f16x8*>(ldv + PLANE + off);
+                        tacc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, bh, tacc[ob], 0, 0, 0);
+                        tacc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ph, bl, tacc[ob], 0, 0, 0);
+                        tacc[ob] = __builtin_amdgcn_mfma_f32_32x32x16_f16(pl, bh, tacc[ob], 0, 0, 0);
+                    }
+                }
+            }
+        };
+        if (ragged) pv_tile(std::true_type{});
+        else pv_tile(std::false_type{});
+        // the tile's 32 terms summed on their own, then added with Kahan compensation (emm_bilinear_f16s.hip: rowstat_update)
+        const float y = t - comp;
+        const float ns = sum + y;
+        comp = (ns - sum) - y;
+        sum = ns;
+
+        if (more) bad |= st.store(lds_all + ((jt + 1) & 1) * STAGE, a.pre, tid, check);
+        __syncthreads();
+    }
+    sum -= comp;
+    const float rsum = sum + shfl_xor_f(sum, 32);          // both halves carry the same reference R
+    if (a.overflow && __any(bad) && lane == 0) atomicOr(a.overflow, 1);
+
+    // ---- store: the lane holds channels l31 and 32 + l31 of queries i0 + mfma32_row(r, h); the row's sum sits in lane (row)
+    const float den = (qok && rsum > 0.f) ? rsum : 0.f;
+    float* const ob0 = a.out + (size_t)n * a.L * a.H * D + (size_t)hh * D + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int rr = mfma32_row(r, h);
+        const float dr = __shfl(den, rr, 64);
+        const int i = i0 + rr;
+        if (i < a.L) {
+#pragma unroll
+            for (int ob = 0; ob < NOB; ++ob) ob0[(size_t)i * a.H * D + 32 * ob] = dr > 0.f ? tacc[ob][r] / dr * a.out_mul : 0.f;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+// The softmax self-attention core of the 8-Point-ViT's Blocks: head dim 64 only, no masks, inference.
+//   out[n, l, h, :] = sum_s softmax_s(q[n,l,h,:] . k[n,s,h,:] / 8) v[n,s,h,:]
+// q row (n, h, l) = q + n q_img + h q_head + l q_row, 64 contiguous floats; k / v rows likewise with the kv strides (floats; every
+// stride a multiple of 4 and the base pointers 16-byte aligned, else FAR_EINVAL).  out: (Z, L, H 64) fp32 contiguous.  D must be 64
+// (anything else: FAR_EINVAL); Z = 0 returns at once; H, L, S >= 1.  act_exp, overflow: as for far_full_attention_f16s.  No workspace.
+int far_vit_attention_f16s(const float* q, const float* k, const float* v, int Z, int L, int S, int H, int D, long q_img, long q_head,
+                           long q_row, long kv_img, long kv_head, long kv_row, int act_exp, float* out, int* overflow,
+                           hipStream_t stream) {
+    far_clear_errors();
+    if (Z == 0) return FAR_OK;
+    if (!q || !k || !v || !out || Z < 0 || L <= 0 || S <= 0 || H <= 0 || D != 64 || act_exp < -24 || act_exp > 8) return FAR_EINVAL;
+    if (((q_img | q_head | q_row | kv_img | kv_head | kv_row) & 3) || q_img < 0 || q_head < 0 || q_row < 64 || kv_img < 0 || kv_head < 0 ||
+        kv_row < 64)
+        return FAR_EINVAL;
+    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || ((uintptr_t)out & 3)) return FAR_EINVAL;
+    Args a;
+    a.q = q; a.k = k; a.v = v; a.out = out; a.overflow = overflow;
+    a.q_img = q_img; a.q_head = q_head; a.q_row = q_row; a.kv_img = kv_img; a.kv_head = kv_head; a.kv_row = kv_row;
+    a.Z = Z; a.L = L; a.S = S; a.H = H;
+    a.nI = (L + ROWS - 1) / ROWS;
+    const long blocks = (long)Z * H * a.nI;
+    if (blocks > 0x7fffffffL || (long)Z * H > 0x7fffffffL) return FAR_EINVAL;
+    a.pre = ldexpf(1.0f, act_exp);
+    a.c1 = ldexpf(1.44269504088896341f / 8.0f, -2 * act_exp);                  // scores -> log2 domain, 1 / sqrt(64)
+    a.out_mul = ldexpf(1.0f, -act_exp);
+    hipLaunchKernelGGL(k_vit_attention, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
+    return far_check_launch();
+}
+
+}  // extern "C"

@@ -123,6 +123,61 @@ def full_attention_train(q, k, v, nhead, q_mask=None, kv_mask=None):
     _, _, _, _, _, q_mask, kv_mask = _full_attention_args(q, k, v, nhead, q_mask, kv_mask)
     return _FullAttentionFn.apply(q, k, v, nhead, q_mask, kv_mask)
 
+def _vit_attention_launch(q, k, v, Z, L, S, nhead, q_strides, kv_strides):
+    """far_vit_attention_f16s on operands whose layout the caller has established (strides in floats: image, head, row)."""
+    lib = _lib.load()
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+        if t.dtype != torch.float32:
+            raise _lib.FarHipError(f'expected dtype {torch.float32}, got {t.dtype}')
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
+        raise NotImplementedError('vit_attention (K23, far_vit_attention_f16s) is an inference kernel: it has no backward; run it '
+                                  'under torch.no_grad() or on tensors that need no gradient')
+    out = torch.empty(Z, L, nhead * 64, dtype=torch.float32, device=q.device)
+    if Z == 0 or L == 0:
+        return out
+    if S == 0:
+        return out.zero_()
+    rc = lib.far_vit_attention_f16s(ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.data_ptr()), Z, L, S,
+                                    nhead, 64, *q_strides, *kv_strides, activation_exponent_value(), _p(out),
+                                    _p(overflow_flag(q.device)), _stream())
+    _lib.check(rc, 'far_vit_attention_f16s')
+    return out
+
+def vit_attention(q, k, v, nhead):
+    """K23: the softmax self-attention core of the 8-Point-ViT's Blocks, head dim 64 only, no masks, inference only.  q: (Z, L, C),
+    k, v: (Z, S, C) fp32 GPU tensors with the heads concatenated (C = nhead * 64; any other head dim raises FarHipError);
+    returns (Z, L, C) = softmax_s(q . k / 8) v per head, on split-fp16 MFMAs with an online softmax (the (L, S) scores never
+    exist).  Operands are split around the thread's activation exponent; a value beyond its range ORs ops.overflow_flag.  Inputs
+    that need gradients raise NotImplementedError (the kernel has no backward).  vit_attention_planes is the same kernel on the
+    head planes the qkv Linear writes."""
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise _lib.FarHipError(f'vit_attention: q (Z, L, C), k, v (Z, S, C); got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}')
+    Z, L, C = q.shape
+    S = k.shape[1]
+    if nhead < 1 or C != nhead * 64:
+        raise _lib.FarHipError(f'vit_attention: head dim 64 only (K23), got {C} channels in {nhead} heads '
+                               '(head dims 16 and 32: ops.full_attention)')
+    q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
+    return _vit_attention_launch(q, k, v, Z, L, S, nhead, (L * C, 64, C), (S * C, 64, C))
+
+def vit_attention_planes(planes, nhead):
+    """K23 on the head planes ops.linear_f16s(x, qkv, out_planes=3 * nhead) writes: planes (3 nhead, Z, N, 64) fp32 contiguous --
+    plane h is q of head h, nhead + h is k, 2 nhead + h is v (the layout K2 reads in place; no copy here either).  Returns
+    (Z, N, nhead * 64) with the heads concatenated: what the `proj` Linear reads.  Checks and refusals as vit_attention."""
+    if not planes.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if planes.dim() != 4 or planes.shape[0] != 3 * nhead or planes.shape[3] != 64 or not planes.is_contiguous():
+        raise _lib.FarHipError(f'vit_attention_planes: planes (3 * nhead, Z, N, 64) contiguous, head dim 64 only (K23); got '
+                               f'{tuple(planes.shape)} for {nhead} heads')
+    _, Z, N, _ = planes.shape
+    st = (N * 64, Z * N * 64, 64)
+    return _vit_attention_launch(planes[:nhead], planes[nhead:2 * nhead], planes[2 * nhead:], Z, N, N, nhead, st, st)
+
 class _LinearAttentionFn(torch.autograd.Function):
     """K5 with its HIP backward (far_linear_attention_f32 / far_linear_attention_bwd_f32)."""
 

@@ -1,0 +1,301 @@
+"""The 8-Point-ViT regressor of FAR (interiornetStreetlearn_8ptVit/src/model.py: ViTEss) behind its ResNet18 extractor, inference only.
+
+Mirrors the module / parameter structure of the reference so that a released checkpoint loads with strict=True after dropping its
+`resnet.*` / `extractor_final_conv.*` entries:
+    fusion_transformer.pos_embed, fusion_transformer.blocks.{i}.{norm1, attn.qkv, attn.proj, norm2, mlp.fc1, mlp.fc2},
+    fusion_transformer.blocks.{depth-1}.{norm1, cross_attn.qkv, cross_attn.proj_fundamental, norm2, mlp.*}, fusion_transformer.norm,
+    pose_regressor.{0, 2, 4}, moe_predictor.{0, 2, 4}
+Reference lines: Attention / Block vision_transformer.py:236-283, CrossBlock :210-234 (far_amd.loftr.transformer.CrossBlock, K2),
+the trunk and the head model.py:171-217, 6D -> matrix tools.py:20-60.
+
+Kernels: K6 (LayerNorm), K9 (qkv into head planes, proj / fc2 with the residual in the epilogue, fc1), K23 (the head-dim-64 softmax
+self-attention, ops.vit_attention_planes), K2 (the CrossBlock), K15 (every Linear of the head).  No eager fallback: CPU tensors raise.
+
+Not built (each raises NotImplementedError): the extractor (torchvision's ResNet18 conv1 .. layer2 + ResidualBlock; `forward(images)`),
+training / gradients through the Blocks, dropout and drop-path (0 in every script), per-sample intrinsics, and the pooled-conv
+ablation (fusion_transformer=False).
+
+Pair order: the reference keeps the two images of pair b in rows 2b, 2b + 1 of a (2B, N, C) tensor; this package's CrossBlock takes
+cat([img0s, img1s]).  forward_features takes and returns the reference's order and converts once, in front of the trunk (the
+Blocks work per image, the CrossBlock's output is per pair in either convention).
+"""
+from functools import partial
+
+import torch
+import torch.nn as nn
+
+from . import _vendor as ag
+from . import ops
+from .loftr.transformer import CrossBlock, Mlp, _init_vit, positional_table_vit
+
+GRID = (24, 24)            # feature_resolution of the reference (model.py:44)
+DIM, HEADS = 192, 3        # total_num_features, num_heads (:43, :64)
+NORM = partial(nn.LayerNorm, eps=1e-6)
+
+
+def update_intrinsics(input_shape, intrinsics):
+    """model.py:120-129 as a pure function: (B, 2, 4) [fx, fy, cx, cy] at the image size input_shape[-2:] -> the same on the 24 x 24
+    feature grid.  Returns a new tensor; the argument is left as it is (the reference scales it in place)."""
+    sizey, sizex = GRID
+    scale = torch.tensor([sizex / input_shape[-1], sizey / input_shape[-2]] * 2, dtype=intrinsics.dtype, device=intrinsics.device)
+    return intrinsics * scale
+
+
+def interleaved_to_concatenated(x):
+    """(2B, ...) with rows (2b, 2b + 1) = pair b  ->  cat([img0s, img1s])."""
+    B = x.shape[0] // 2
+    return x.reshape(B, 2, *x.shape[1:]).transpose(0, 1).reshape(x.shape)
+
+
+def concatenated_to_interleaved(x):
+    """cat([img0s, img1s])  ->  (2B, ...) with rows (2b, 2b + 1) = pair b."""
+    B = x.shape[0] // 2
+    return x.reshape(2, B, *x.shape[1:]).transpose(0, 1).reshape(x.shape)
+
+
+def rotation_matrix_from_ortho6d(o6):
+    """tools.py:47-60 (Gram-Schmidt, the norms floored at 1e-8 as normalize_vector :20-29): (B, 6) -> (B, 3, 3), columns x, y, z."""
+    floor = torch.tensor(1e-8, dtype=o6.dtype, device=o6.device)
+    unit = lambda v: v / torch.max(torch.sqrt(v.pow(2).sum(1)), floor).unsqueeze(1)
+    x = unit(o6[:, 0:3])
+    z = unit(torch.cross(x, o6[:, 3:6], dim=1))
+    y = torch.cross(z, x, dim=1)
+    return torch.stack([x, y, z], dim=2)
+
+
+def pose_from_rotation_matrix(T_pose, r):
+    """tools.py:9-17: (J, 3) rest poses under the (B, 3, 3) rotations -> (B, J, 3)."""
+    return torch.matmul(r.unsqueeze(1), T_pose.to(r).reshape(1, -1, 3, 1)).squeeze(-1)
+
+
+def loftr_gate_inputs(data):
+    """The gate's inputs from the data dict far_amd.pipeline / supervision.spvs_RT fill: -> (loftr_preds (B, 4, 4) fp32,
+    loftr_num_corr (B,) fp32) from data['loftr_rt'] ((3, 4) for one pair, else (B, 3, 4)) and
+    data['num_correspondences_after_ransac'] -- what the reference reads from cached prediction files."""
+    rt = data['loftr_rt']
+    rt = (rt.unsqueeze(0) if rt.dim() == 2 else rt).detach().float()
+    B = rt.shape[0]
+    bottom = torch.tensor([0., 0., 0., 1.], device=rt.device).expand(B, 1, 4)
+    n = data['num_correspondences_after_ransac']
+    n = n if torch.is_tensor(n) else torch.as_tensor(n)
+    return torch.cat([rt, bottom], dim=1), n.detach().to(rt.device).float().reshape(-1).expand(B).contiguous()
+
+
+def _no_drop(**rates):
+    for name, r in rates.items():
+        if r:
+            raise NotImplementedError(f'{name}={r}: dropout / drop-path are 0 in every 8-Point-ViT script and exist in training only; '
+                                      'this package builds the inference path')
+
+
+class Attention(nn.Module):
+    """vision_transformer.py:236-262: the qkv Linear on K9 straight into head planes, K23, `proj` on K9 (the Block adds the residual
+    in its epilogue).  Head dim 64 only."""
+
+    def __init__(self, dim, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
+        super().__init__()
+        _no_drop(attn_drop=attn_drop, proj_drop=proj_drop)
+        if dim != num_heads * 64:
+            raise NotImplementedError(f'Attention: head dim {dim // num_heads} -- K23 (far_vit_attention_f16s) is a head-dim-64 kernel')
+        self.num_heads = num_heads
+        self.scale = (dim // num_heads) ** -0.5
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.proj = nn.Linear(dim, dim)
+
+    def forward(self, x, residual=None):
+        pk = self.__dict__.setdefault('_packs', ops.PackCache())
+        qkv_t = [self.qkv.weight] + ([self.qkv.bias] if self.qkv.bias is not None else [])
+        pq = pk.get('qkv', qkv_t, lambda: ops.PackedConv(self.qkv.weight, None, self.qkv.bias))
+        pp = pk.get('proj', [self.proj.weight, self.proj.bias], lambda: ops.PackedConv(self.proj.weight, None, self.proj.bias))
+        planes = ops.linear_f16s(x.contiguous(), pq, out_planes=3 * self.num_heads)          # (3h, Z, N, 64)
+        a = ops.vit_attention_planes(planes, self.num_heads)                                # (Z, N, C), heads concatenated
+        return ops.linear_f16s(a, pp, residual=None if residual is None else residual.contiguous())
+
+
+class Block(nn.Module):
+    """vision_transformer.py:265-283: x + attn(norm1(x)), then x + mlp(norm2(x)); K6, K9, K23, K9, K6, K9, K9."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., drop_path=0., act_layer=nn.GELU,
+                 norm_layer=nn.LayerNorm):
+        super().__init__()
+        _no_drop(drop=drop, attn_drop=attn_drop, drop_path=drop_path)
+        self.norm1 = norm_layer(dim)
+        self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias)
+        self.norm2 = norm_layer(dim)
+        self.mlp = Mlp(in_features=dim, hidden_features=int(dim * mlp_ratio), act_layer=act_layer)
+
+    def forward(self, x, intrinsics=None):
+        if ag.needs_grad(x, self.norm1.weight):
+            raise NotImplementedError('vit8pt.Block: training / gradients through the ViT blocks are not built -- K23 '
+                                      '(far_vit_attention_f16s) has no backward; call it under torch.no_grad()')
+        x = x.contiguous()
+        x = self.attn(ops.layernorm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps), residual=x)
+        return self.mlp(ops.layernorm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps), residual=x)
+
+
+class FusionTransformer(nn.Module):
+    """The reference's trimmed VisionTransformer (model.py:63-79, :171-180): x + pos_embed, depth - 1 Blocks, the CrossBlock, the
+    final LayerNorm.  forward takes cat([img0s, img1s]) (2B, 576, 192) and returns (2B, 70, 192), rows (2b, 2b + 1) = pair b.
+
+    intrinsics: None (the plain table) or one camera's (fx, fy, cx, cy) on the 24 x 24 grid; one positional table is built per
+    distinct value and kept (both datasets have one camera)."""
+
+    def __init__(self, embed_dim=DIM, depth=6, num_heads=HEADS, mlp_ratio=4., qkv_bias=True, drop_rate=0., attn_drop_rate=0.,
+                 drop_path_rate=0.):
+        super().__init__()
+        _no_drop(drop_rate=drop_rate, attn_drop_rate=attn_drop_rate, drop_path_rate=drop_path_rate)
+        if depth < 1:
+            raise ValueError('transformer_depth >= 1: the last block is the CrossBlock')
+        self.num_patches = GRID[0] * GRID[1]
+        self.pos_embed = nn.Parameter(torch.zeros(1, self.num_patches, embed_dim))
+        blocks = [Block(embed_dim, num_heads, mlp_ratio, qkv_bias, norm_layer=NORM) for _ in range(depth - 1)]
+        blocks.append(CrossBlock(embed_dim, num_heads, mlp_ratio, qkv_bias, norm_layer=NORM, pos=positional_table_vit(*GRID, None)))
+        self.blocks = nn.Sequential(*blocks)
+        self.norm = NORM(embed_dim)
+        self.apply(_init_vit)
+        nn.init.xavier_uniform_(self.pos_embed)                    # model.py:77-79
+        self._tables = {}
+
+    def _table(self, key, device):
+        t = self._tables.get((key, str(device)))
+        if t is None:
+            t = self._tables[(key, str(device))] = positional_table_vit(*GRID, key).to(device)
+        return t
+
+    def forward(self, x, intrinsics=None, taps=None):
+        """taps: optional list that receives every block's output (tests)."""
+        if ag.needs_grad(x, self.pos_embed):
+            raise NotImplementedError('vit8pt.FusionTransformer: training / gradients are not built (K23, far_vit_attention_f16s, '
+                                      'has no backward); call it under torch.no_grad()')
+        if not x.is_cuda:
+            raise ops._lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+        cross = self.blocks[-1]
+        cross.cross_attn.pos6 = self._table(None if intrinsics is None else tuple(float(v) for v in intrinsics), x.device)
+        x = x + self.pos_embed
+        for blk in self.blocks:
+            x = blk(x)
+            if taps is not None:
+                taps.append(x)
+        return ops.layernorm(x.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps)
+
+
+def _one_camera(intrinsics):
+    """(B, 2, 4) -> the (fx, fy, cx, cy) every frame of the batch shares (host floats)."""
+    k = intrinsics.detach().float().cpu()
+    if k.dim() != 3 or tuple(k.shape[1:]) != (2, 4):
+        raise ValueError(f'intrinsics: (B, 2, 4) [fx, fy, cx, cy] per frame on the feature grid, got {tuple(k.shape)}')
+    if not bool(torch.all(k[:, 0] == k[:, 1])):
+        raise ValueError('intrinsics differ between the two frames of a pair (the reference asserts they are equal, '
+                         'vision_transformer.py:117)')
+    if not bool(torch.all(k[:, 0] == k[0, 0])):
+        raise NotImplementedError('per-sample intrinsics: the pairs of this batch have different cameras; one positional table per '
+                                  'call is built (both datasets have one camera) -- split the batch by camera')
+    return tuple(float(v) for v in k[0, 0])
+
+
+class ViTEss(nn.Module):
+    """model.py:38-217 without the extractor.  args: fusion_transformer (must be True), transformer_depth, fc_hidden_size, pool_size
+    (read, unused on this path), use_loftr_gating, use_normalized_6d, T_pose (J, 3).  global_pose_mean / global_pose_std: (9,)
+    tensors, needed with use_normalized_6d (plain attributes as in the reference: not part of the state dict)."""
+
+    def __init__(self, args, global_pose_mean=None, global_pose_std=None):
+        super().__init__()
+        self.total_num_features = DIM
+        self.feature_resolution = GRID
+        self.pose_size = 9
+        self.num_patches = GRID[0] * GRID[1]
+        self.H2 = args.fc_hidden_size
+        self.use_loftr_gating = args.use_loftr_gating
+        self.use_normalized_6d = args.use_normalized_6d
+        self.global_pose_mean = global_pose_mean
+        self.global_pose_std = global_pose_std
+        if not args.fusion_transformer:
+            raise NotImplementedError('fusion_transformer=False (the pooled-conv ablation, model.py:83-91) is not built')
+        self.num_heads = HEADS
+        self.transformer_depth = args.transformer_depth
+        self.fusion_transformer = FusionTransformer(DIM, args.transformer_depth, HEADS)
+        self.H = int(HEADS * 2 * (DIM // HEADS + 6) * (DIM // HEADS))                       # 26880
+        H, H2 = self.H, self.H2
+        if self.use_loftr_gating:
+            self.moe_predictor = nn.Sequential(nn.Linear(H + 2 * self.pose_size + 1, H2), nn.ReLU(), nn.Linear(H2, H2), nn.ReLU(),
+                                               nn.Linear(H2, 2), nn.Sigmoid())
+        self.pose_regressor = nn.Sequential(nn.Linear(H, H2), nn.ReLU(), nn.Linear(H2, H2), nn.ReLU(), nn.Linear(H2, self.pose_size))
+        self.T_pose = args.T_pose
+
+    update_intrinsics = staticmethod(update_intrinsics)
+
+    def forward(self, images, intrinsics=None, inference=False, loftr_num_corr=None, loftr_preds=None):
+        raise NotImplementedError('ViTEss.forward(images): the extractor (torchvision ResNet18 conv1 .. layer2 + ResidualBlock, '
+                                  'model.py:131-163) is not built -- torchvision is not a dependency of this package.  Run it '
+                                  'elsewhere and call forward_features(features, intrinsics, loftr_num_corr, loftr_preds) with its '
+                                  '(2B, 576, 192) output and update_intrinsics(images.shape, intrinsics)')
+
+    def trunk(self, features, intrinsics=None, taps=None):
+        """(2B, 576, 192) extractor output in the reference's pair order -> the (2B, 70, 192) normalised features (model.py:171-180).
+        taps (tests): receives each block's output, Blocks in the reference's pair order."""
+        if features.dim() != 3 or features.shape[0] % 2 or tuple(features.shape[1:]) != (self.num_patches, DIM):
+            raise ValueError(f'features: (2B, {self.num_patches}, {DIM}) with rows (2b, 2b + 1) = pair b, got {tuple(features.shape)}')
+        cam = None if intrinsics is None else _one_camera(intrinsics)
+        got = None if taps is None else []
+        out = self.fusion_transformer(interleaved_to_concatenated(features.float()), cam, got)
+        if taps is not None:
+            taps.extend([concatenated_to_interleaved(t) for t in got[:-1]] + got[-1:])
+        return out
+
+    def forward_features(self, features, intrinsics=None, loftr_num_corr=None, loftr_preds=None):
+        """model.py:171-217 from the extractor's output.  features: (2B, 576, 192) fp32 on the GPU, rows (2b, 2b + 1) = the two images
+        of pair b; intrinsics: None or (B, 2, 4) [fx, fy, cx, cy] ON THE FEATURE GRID (update_intrinsics), equal in both frames
+        (ValueError otherwise) and, in this package, equal for every pair of the batch -- differing cameras raise
+        NotImplementedError; loftr_preds (B, 4, 4), loftr_num_corr (B,): the solver's pose and inlier count (loftr_gate_inputs),
+        needed with use_loftr_gating.  Returns the reference's (tran_preds_unnorm (B, 3), rot_preds (B, J, 3), rot_preds_mtx
+        (B, 3, 3), rot_preds_6d (B, 6)).  Pair b's outputs do not depend on the batch it is computed in."""
+        feats = self.trunk(features, intrinsics)
+        B = feats.shape[0] // 2
+        feats = feats.reshape(B, -1)                                                       # (B, 26880)
+        dev = feats.device
+        pk = self.__dict__.setdefault('_packs', ops.PackCache())
+        lin = lambda name, m, **kw: pk.get(name, [m.weight, m.bias], lambda: ops.PackedRows(m.weight, m.bias, **kw))
+        reg = self.pose_regressor
+        mean = std = None
+        if self.use_normalized_6d:
+            if self.global_pose_mean is None or self.global_pose_std is None:
+                raise ValueError('use_normalized_6d needs global_pose_mean and global_pose_std')
+            mean, std = self.global_pose_mean.to(dev).float(), self.global_pose_std.to(dev).float()
+        if self.use_loftr_gating:
+            if loftr_preds is None or loftr_num_corr is None:
+                raise ValueError('use_loftr_gating needs loftr_preds (B, 4, 4) and loftr_num_corr (B,)')
+            moe = self.moe_predictor
+            # the two 26880-wide first layers read the features only: one K15 launch for both (no bias yet)
+            both = pk.get('reg0|moe0', [reg[0].weight, moe[0].weight],
+                          lambda: ops.PackedRows(torch.cat([reg[0].weight, moe[0].weight[:, :self.H]], 0)))
+            pre = ops.rows_linear(feats, both)                                             # (B, 2 H2)
+            h = torch.relu(pre[:, :self.H2] + reg[0].bias)
+        else:
+            h = ops.rows_linear(feats, lin('reg0', reg[0]), act='relu')
+        h = ops.rows_linear(h, lin('reg2', reg[2]), act='relu')
+        pred_reg_6d = ops.rows_linear(h, lin('reg4', reg[4]))                              # (B, 9)
+        if self.use_loftr_gating:
+            rt = loftr_preds.to(dev).float()
+            solver_6d = torch.cat([rt[..., :3, 3], rt[..., :2, :3].reshape(B, 6)], dim=-1)      # compute_6d, model.py:11-30
+            if self.use_normalized_6d:
+                solver_6d = (solver_6d - mean) / std
+            ncorr = loftr_num_corr.detach().to(dev).float().reshape(B, 1) / 500
+            solver_6d = torch.cat([solver_6d, ncorr], dim=-1)                              # (B, 10)
+            tail = torch.cat([pred_reg_6d, solver_6d], dim=-1).contiguous()                # (B, 19)
+            g = ops.rows_linear(tail, lin('moe0-tail', moe[0], cols=(self.H, moe[0].weight.shape[1])), act='relu',
+                                add=pre[:, self.H2:])
+            g = ops.rows_linear(g, lin('moe2', moe[2]), act='relu')
+            wt = ops.rows_linear(g, lin('moe4', moe[4]), act='sigmoid')                    # (B, 2)
+            pred_T = wt[..., :1] * pred_reg_6d[..., :3] + (1 - wt[..., :1]) * solver_6d[..., :3]
+            pred_R = wt[..., 1:] * pred_reg_6d[..., 3:] + (1 - wt[..., 1:]) * solver_6d[..., 3:-1]
+            pose = torch.cat([pred_T, pred_R], dim=-1)
+        else:
+            pose = pred_reg_6d
+        rot_6d, tran = pose[:, 3:], pose[:, :3]
+        if self.use_normalized_6d:
+            rot_unnorm = rot_6d * std[3:] + mean[3:]
+            tran_unnorm = tran * std[:3] + mean[:3]
+        else:
+            rot_unnorm, tran_unnorm = rot_6d, tran
+        mtx = rotation_matrix_from_ortho6d(rot_unnorm)
+        return tran_unnorm, pose_from_rotation_matrix(self.T_pose, mtx), mtx, rot_6d

@@ -344,6 +344,21 @@ int far_full_attention_f16s(const float* q, const float* k, const float* v, int 
                             const uint8_t* q_mask, const uint8_t* kv_mask, int act_exp, float* out, void* ws,
                             int* overflow, far_stream_t stream);
 
+/* K23: the softmax self-attention core of the 8-Point-ViT's Blocks (vision_transformer.py:250-258; vit_attention_f16s.hip), inference:
+ *   out[n, l, h, :] = sum_s softmax_s(q[n,l,h,:] . k[n,s,h,:] / 8) v[n,s,h,:],   head dim D = 64 only (anything else: -22), no masks
+ * on split-fp16 MFMAs with an online softmax over 64-key tiles: the (Z, H, L, S) score tensor never exists.  Row (n, h, l) of q is the
+ * 64 contiguous floats at q + n q_img + h q_head + l q_row; rows of k and v likewise with the kv_* strides (in floats; every stride
+ * a multiple of 4, rows at least 64 apart, base pointers 16-byte aligned, else -22): the head planes [3H][Z][N][64] that
+ * far_conv_nhwc_f32 writes with out_planes = 3H (q = plane h, k = plane H + h, v = plane 2H + h: img = N 64, head = Z N 64, row = 64)
+ * and the concatenated [Z][N][H*64] form (img = N H 64, head = 64, row = H 64) are both read in place.  out: [Z][L][H*64] fp32
+ * contiguous, heads concatenated.  H, L, S >= 1; Z = 0 returns at once.  Keys past S of the last tile are selected out, query tails
+ * are exact.  act_exp: q, k, v are multiplied by 2^act_exp before the fp16 split (4 = the default; -24 .. 8): values up to
+ * 65504 / 2^act_exp survive it.  overflow: device int or NULL, |= 1 when a value that takes part is beyond that range or not finite
+ * (out then holds inf / NaN).  No workspace, no float atomics; an image's output bits do not depend on the batch it is computed in. */
+int far_vit_attention_f16s(const float* q, const float* k, const float* v, int Z, int L, int S, int H, int D, long q_img, long q_head,
+                           long q_row, long kv_img, long kv_head, long kv_row, int act_exp, float* out, int* overflow,
+                           far_stream_t stream);
+
 /* K22 under autograd (full_attention_f16s.hip, full_attention_bwd_f16s.hip).
  * far_full_attention_train_f16s: far_full_attention_f16s -- the same launches, the same `out` bits, the same workspace -- that also
  * writes lse [N][H][L] fp32: the log2-domain log-sum-exp of row l's scaled scores (+1e30 for a padded query row and for every row of
