@@ -74,6 +74,9 @@ SIGNATURES = {
     'far_full_attention_bwd_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     'far_full_attention_bwd_f16s': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     'far_vit_attention_f16s': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_l, c_l, c_l, c_i, c_p, c_p, c_p]),
+    'far_vit_attention_train_f16s': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_l, c_l, c_l, c_i, c_p, c_p, c_p, c_p]),
+    'far_vit_attention_bwd_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
+    'far_vit_attention_bwd_f16s': (c_i, [c_p] * 6 + [c_i] * 5 + [c_l] * 6 + [c_i, c_p, c_p, c_p] + [c_l] * 6 + [c_p, c_p, c_p]),
     'far_linear_attention_bwd_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     'far_linear_attention_bwd_f32': (c_i, [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_f, c_p, c_p, c_p, c_p, c_p]),
     'far_layernorm_f32': (c_i, [c_p, c_p, c_p, c_p, c_l, c_i, c_f, c_p, c_p]),

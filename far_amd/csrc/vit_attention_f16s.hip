@@ -49,6 +49,7 @@ __device__ __forceinline__ int row_off(int row, int c) { return row * 128 + ((c 
 struct Args {
     const float *q, *k, *v;
     float* out;
+    float* lse;            // training forward: (Z, H, L) log2-domain log-sum-exp of each row (NULL: inference)
     int* overflow;
     long q_img, q_head, q_row, kv_img, kv_head, kv_row;     // strides in floats
     int Z, L, S, H, nI;
@@ -298,6 +299,8 @@ __global__ __launch_bounds__(NT, 2) void k_vit_attention(Args a) {
 
     // ---- store: the lane holds channels l31 and 32 + l31 of queries i0 + mfma32_row(r, h); the row's sum sits in lane (row)
     const float den = (qok && rsum > 0.f) ? rsum : 0.f;
+    // the row statistic the backward recomputes p from: p = 2^(x - R + 15) / rsum = 2^(x - lse2), in the units of the unscaled inputs
+    if (a.lse && h == 0 && qok) a.lse[(size_t)z * a.L + irow] = den > 0.f ? (float)(R - P_EXP) + log2f(rsum) : 1.0e30f;
     float* const ob0 = a.out + (size_t)n * a.L * a.H * D + (size_t)hh * D + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -309,6 +312,31 @@ __global__ __launch_bounds__(NT, 2) void k_vit_attention(Args a) {
             for (int ob = 0; ob < NOB; ++ob) ob0[(size_t)i * a.H * D + 32 * ob] = dr > 0.f ? tacc[ob][r] / dr * a.out_mul : 0.f;
         }
     }
+}
+
+// The one launch behind both entry points: the same geometry and arithmetic, lse written when non-null.
+static int launch_forward(const float* q, const float* k, const float* v, int Z, int L, int S, int H, int D, long q_img, long q_head,
+                          long q_row, long kv_img, long kv_head, long kv_row, int act_exp, float* out, float* lse, int* overflow,
+                          hipStream_t stream) {
+    far_clear_errors();
+    if (Z == 0) return FAR_OK;
+    if (!q || !k || !v || !out || Z < 0 || L <= 0 || S <= 0 || H <= 0 || D != 64 || act_exp < -24 || act_exp > 8) return FAR_EINVAL;
+    if (((q_img | q_head | q_row | kv_img | kv_head | kv_row) & 3) || q_img < 0 || q_head < 0 || q_row < 64 || kv_img < 0 || kv_head < 0 ||
+        kv_row < 64)
+        return FAR_EINVAL;
+    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || ((uintptr_t)out & 3) || ((uintptr_t)lse & 3)) return FAR_EINVAL;
+    Args a;
+    a.q = q; a.k = k; a.v = v; a.out = out; a.lse = lse; a.overflow = overflow;
+    a.q_img = q_img; a.q_head = q_head; a.q_row = q_row; a.kv_img = kv_img; a.kv_head = kv_head; a.kv_row = kv_row;
+    a.Z = Z; a.L = L; a.S = S; a.H = H;
+    a.nI = (L + ROWS - 1) / ROWS;
+    const long blocks = (long)Z * H * a.nI;
+    if (blocks > 0x7fffffffL || (long)Z * H > 0x7fffffffL) return FAR_EINVAL;
+    a.pre = ldexpf(1.0f, act_exp);
+    a.c1 = ldexpf(1.44269504088896341f / 8.0f, -2 * act_exp);                  // scores -> log2 domain, 1 / sqrt(64)
+    a.out_mul = ldexpf(1.0f, -act_exp);
+    hipLaunchKernelGGL(k_vit_attention, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
+    return far_check_launch();
 }
 
 }  // namespace
@@ -323,25 +351,16 @@ extern "C" {
 int far_vit_attention_f16s(const float* q, const float* k, const float* v, int Z, int L, int S, int H, int D, long q_img, long q_head,
                            long q_row, long kv_img, long kv_head, long kv_row, int act_exp, float* out, int* overflow,
                            hipStream_t stream) {
-    far_clear_errors();
-    if (Z == 0) return FAR_OK;
-    if (!q || !k || !v || !out || Z < 0 || L <= 0 || S <= 0 || H <= 0 || D != 64 || act_exp < -24 || act_exp > 8) return FAR_EINVAL;
-    if (((q_img | q_head | q_row | kv_img | kv_head | kv_row) & 3) || q_img < 0 || q_head < 0 || q_row < 64 || kv_img < 0 || kv_head < 0 ||
-        kv_row < 64)
-        return FAR_EINVAL;
-    if ((((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) & 15) || ((uintptr_t)out & 3)) return FAR_EINVAL;
-    Args a;
-    a.q = q; a.k = k; a.v = v; a.out = out; a.overflow = overflow;
-    a.q_img = q_img; a.q_head = q_head; a.q_row = q_row; a.kv_img = kv_img; a.kv_head = kv_head; a.kv_row = kv_row;
-    a.Z = Z; a.L = L; a.S = S; a.H = H;
-    a.nI = (L + ROWS - 1) / ROWS;
-    const long blocks = (long)Z * H * a.nI;
-    if (blocks > 0x7fffffffL || (long)Z * H > 0x7fffffffL) return FAR_EINVAL;
-    a.pre = ldexpf(1.0f, act_exp);
-    a.c1 = ldexpf(1.44269504088896341f / 8.0f, -2 * act_exp);                  // scores -> log2 domain, 1 / sqrt(64)
-    a.out_mul = ldexpf(1.0f, -act_exp);
-    hipLaunchKernelGGL(k_vit_attention, dim3((unsigned)blocks), dim3(NT), 0, stream, a);
-    return far_check_launch();
+    return launch_forward(q, k, v, Z, L, S, H, D, q_img, q_head, q_row, kv_img, kv_head, kv_row, act_exp, out, nullptr, overflow, stream);
+}
+
+// far_vit_attention_f16s under autograd: the same launch, the same `out` bits, plus the row statistic the backward
+// (vit_attention_bwd_f16s.hip) recomputes the probabilities from: lse (Z, H, L) fp32, lse[z, h, l] = log2 sum_s 2^(log2(e) q_l.k_s / 8).
+int far_vit_attention_train_f16s(const float* q, const float* k, const float* v, int Z, int L, int S, int H, int D, long q_img,
+                                 long q_head, long q_row, long kv_img, long kv_head, long kv_row, int act_exp, float* out, float* lse,
+                                 int* overflow, hipStream_t stream) {
+    if (Z != 0 && !lse) return FAR_EINVAL;
+    return launch_forward(q, k, v, Z, L, S, H, D, q_img, q_head, q_row, kv_img, kv_head, kv_row, act_exp, out, lse, overflow, stream);
 }
 
 }  // extern "C"

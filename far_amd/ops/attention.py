@@ -1,4 +1,4 @@
-"""far_amd.ops.attention: K5 linear attention, K22 full attention and K6 LayerNorm (forward, backward, training wrappers) (one family of the torch-tensor front ends for the C ABI in include/far_hip.h; far_amd/ops/__init__.py
+"""far_amd.ops.attention: K5 linear attention, K22 full attention, K23 head-dim-64 attention and K6 LayerNorm (forward, backward, training wrappers) (one family of the torch-tensor front ends for the C ABI in include/far_hip.h; far_amd/ops/__init__.py
 re-exports everything under the flat far_amd.ops namespace the rest of the package uses)."""
 import ctypes
 import os
@@ -132,8 +132,9 @@ def _vit_attention_launch(q, k, v, Z, L, S, nhead, q_strides, kv_strides):
         if t.dtype != torch.float32:
             raise _lib.FarHipError(f'expected dtype {torch.float32}, got {t.dtype}')
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
-        raise NotImplementedError('vit_attention (K23, far_vit_attention_f16s) is an inference kernel: it has no backward; run it '
-                                  'under torch.no_grad() or on tensors that need no gradient')
+        raise NotImplementedError('vit_attention (K23, far_vit_attention_f16s) is the inference front end: run it under torch.no_grad() '
+                                  'or on tensors that need no gradient; ops.vit_attention_train / vit_attention_train_qkv are the '
+                                  'forms with the HIP backward')
     out = torch.empty(Z, L, nhead * 64, dtype=torch.float32, device=q.device)
     if Z == 0 or L == 0:
         return out
@@ -150,8 +151,8 @@ def vit_attention(q, k, v, nhead):
     k, v: (Z, S, C) fp32 GPU tensors with the heads concatenated (C = nhead * 64; any other head dim raises FarHipError);
     returns (Z, L, C) = softmax_s(q . k / 8) v per head, on split-fp16 MFMAs with an online softmax (the (L, S) scores never
     exist).  Operands are split around the thread's activation exponent; a value beyond its range ORs ops.overflow_flag.  Inputs
-    that need gradients raise NotImplementedError (the kernel has no backward).  vit_attention_planes is the same kernel on the
-    head planes the qkv Linear writes."""
+    that need gradients raise NotImplementedError (vit_attention_train is the form with gradients).  vit_attention_planes is the
+    same kernel on the head planes the qkv Linear writes."""
     for t in (q, k, v):
         if not t.is_cuda:
             raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
@@ -177,6 +178,138 @@ def vit_attention_planes(planes, nhead):
     _, Z, N, _ = planes.shape
     st = (N * 64, Z * N * 64, 64)
     return _vit_attention_launch(planes[:nhead], planes[nhead:2 * nhead], planes[2 * nhead:], Z, N, N, nhead, st, st)
+
+def _vit_views(q, k, v, nhead, what):
+    """The checks of vit_attention on (Z, L | S, nhead * 64) fp32 GPU tensors whose rows are contiguous (views into a wider
+    projection included) -> (Z, L, S, C, q strides, kv strides), strides in floats as (image, head, row)."""
+    for t in (q, k, v):
+        if not t.is_cuda:
+            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
+        raise _lib.FarHipError(f'{what}: q (Z, L, C), k, v (Z, S, C); got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}')
+    Z, L, C = q.shape
+    S = k.shape[1]
+    if nhead < 1 or C != nhead * 64:
+        raise _lib.FarHipError(f'{what}: head dim 64 only (K23), got {C} channels in {nhead} heads '
+                               '(head dims 16 and 32: ops.full_attention_train)')
+    for t in (q, k, v):
+        if t.dtype != torch.float32:
+            raise _lib.FarHipError(f'expected dtype {torch.float32}, got {t.dtype}')
+    return Z, L, S, C
+
+def _row_strides(t):
+    """(image, head, row) strides in floats of a (Z, rows, nhead * 64) view with contiguous rows."""
+    if t.numel() and t.stride(2) != 1:
+        raise _lib.FarHipError('K23 needs rows of contiguous floats')
+    return (t.stride(0), 64, t.stride(1))
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+def _vit_train_forward(q, k, v, Z, L, S, nhead):
+    """far_vit_attention_train_f16s on views with contiguous rows -> (out (Z, L, C), lse (Z, nhead, L), the activation exponent)."""
+    lib = _lib.load()
+    out = torch.empty(Z, L, nhead * 64, dtype=torch.float32, device=q.device)
+    lse = torch.empty(Z, nhead, L, dtype=torch.float32, device=q.device)
+    act_exp = activation_exponent_value()
+    if Z and L and S:
+        if k.stride() != v.stride():
+            raise _lib.FarHipError('K23: k and v must share their strides')
+        rc = lib.far_vit_attention_train_f16s(_ptr(q), _ptr(k), _ptr(v), Z, L, S, nhead, 64, *_row_strides(q), *_row_strides(k), act_exp,
+                                              _p(out), _p(lse), _p(overflow_flag(q.device)), _stream())
+        _lib.check(rc, 'far_vit_attention_train_f16s')
+    else:
+        out.zero_()                     # no key: exact zeros (as vit_attention)
+        lse.zero_()
+    return out, lse, act_exp
+
+def vit_attention_bwd(q, k, v, out, lse, g, nhead, act_exp=None, into=None):
+    """K23 backward (far_vit_attention_bwd_f16s): (dq, dk, dv) for the output gradient g, from q (Z, L, C), k, v (Z, S, C) -- fp32
+    GPU tensors with contiguous rows; the three column slices of one (Z, N, 3 C) projection are read in place --, the output and the
+    (Z, nhead, L) row statistic of the training forward (same activation exponent).  into: None (three new contiguous tensors) or one
+    (Z, N, 3 C) fp32 contiguous tensor (L = S = N) whose column slices [0, C), [C, 2 C), [2 C, 3 C) the kernels write dq, dk, dv
+    into, returned as views of it.  Z = 0, L = 0 or S = 0: zeros."""
+    lib = _lib.load()
+    Z, L, S, C = _vit_views(q, k, v, nhead, 'vit_attention_bwd')
+    if not g.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    g = g.float().contiguous()
+    if tuple(g.shape) != (Z, L, C) or tuple(out.shape) != (Z, L, C) or tuple(lse.shape) != (Z, nhead, L):
+        raise _lib.FarHipError(f'vit_attention_bwd: out, g (Z, L, C) and lse (Z, nhead, L); got {tuple(out.shape)}, {tuple(g.shape)}, '
+                               f'{tuple(lse.shape)}')
+    if into is None:
+        dq = torch.empty(Z, L, C, dtype=torch.float32, device=q.device)
+        dk, dv = (torch.empty(Z, S, C, dtype=torch.float32, device=q.device) for _ in range(2))
+    else:
+        if tuple(into.shape) != (Z, L, 3 * C) or L != S or into.dtype != torch.float32 or not into.is_cuda or not into.is_contiguous():
+            raise _lib.FarHipError(f'vit_attention_bwd: `into` must be (Z, N, 3 C) fp32 contiguous on the GPU with L = S = N, got '
+                                   f'{tuple(into.shape)}')
+        dq, dk, dv = into[..., :C], into[..., C:2 * C], into[..., 2 * C:]
+    if not (Z and L and S):
+        if into is not None:
+            into.zero_()
+        else:
+            dq.zero_(); dk.zero_(); dv.zero_()
+        return dq, dk, dv
+    if k.stride() != v.stride():
+        raise _lib.FarHipError('K23: k and v must share their strides')
+    ws = _ws(lib.far_vit_attention_bwd_workspace_bytes(Z, L, S, nhead, 64), q.device)
+    rc = lib.far_vit_attention_bwd_f16s(_ptr(q), _ptr(k), _ptr(v), _p(out, torch.float32), _p(lse, torch.float32), _p(g, torch.float32),
+                                        Z, L, S, nhead, 64, *_row_strides(q), *_row_strides(k),
+                                        activation_exponent_value() if act_exp is None else act_exp, _ptr(dq), _ptr(dk), _ptr(dv),
+                                        *_row_strides(dq), *_row_strides(dk), _p(ws), _p(overflow_flag(q.device)), _stream())
+    _lib.check(rc, 'far_vit_attention_bwd_f16s')
+    if into is not None:
+        _written(into)
+    return dq, dk, dv
+
+class _VitAttentionFn(torch.autograd.Function):
+    """K23 with its HIP backward (far_vit_attention_train_f16s / far_vit_attention_bwd_f16s).  packed: the one tensor is a
+    (Z, N, 3 C) qkv projection read in place, its gradient one (Z, N, 3 C) tensor the kernels write in place; else q, k, v.  Saved:
+    q, k, v (or the one qkv tensor), the output, the (Z, H, L) row statistic and the activation exponent -- nothing of size (L, S)."""
+
+    @staticmethod
+    def forward(ctx, nhead, packed, *ts):
+        ts = tuple(t.detach().contiguous() for t in ts)
+        C = nhead * 64
+        q, k, v = (ts[0][..., :C], ts[0][..., C:2 * C], ts[0][..., 2 * C:]) if packed else ts
+        Z, L, S = q.shape[0], q.shape[1], k.shape[1]
+        out, lse, act_exp = _vit_train_forward(q, k, v, Z, L, S, nhead)
+        ctx.save_for_backward(*ts, out, lse)
+        ctx.nhead, ctx.packed, ctx.act_exp = nhead, packed, act_exp
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        *ts, out, lse = ctx.saved_tensors
+        C = ctx.nhead * 64
+        if ctx.packed:
+            qkv = ts[0]
+            dqkv = torch.empty_like(qkv)
+            vit_attention_bwd(qkv[..., :C], qkv[..., C:2 * C], qkv[..., 2 * C:], out, lse, g, ctx.nhead, ctx.act_exp, into=dqkv)
+            return None, None, dqkv
+        return (None, None) + tuple(vit_attention_bwd(*ts, out, lse, g, ctx.nhead, ctx.act_exp))
+
+def vit_attention_train(q, k, v, nhead):
+    """K23 with gradients: the arguments, checks, edge cases and output bits of vit_attention; (dq, dk, dv) come from the HIP
+    backward (recomputed score tiles, nothing of size (L, S) is saved or allocated).  Z = 0, L = 0 or S = 0: zeros with zero
+    gradients."""
+    _vit_views(q, k, v, nhead, 'vit_attention_train')
+    return _VitAttentionFn.apply(nhead, False, q, k, v)
+
+def vit_attention_train_qkv(qkv, nhead):
+    """K23 with gradients on one (Z, N, 3 nhead 64) qkv projection, columns t C + h 64 + d (t = 0, 1, 2 for q, k, v: the
+    reference's reshape(B, N, 3, H, 64), vision_transformer.py:252): q, k, v are read in place, and the backward returns ONE
+    (Z, N, 3 C) gradient that the kernels wrote in place -- no chunk, no cat, no copies.  Returns (Z, N, C), heads concatenated:
+    the bits of vit_attention_train on the three column slices."""
+    if not qkv.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if qkv.dim() != 3 or nhead < 1 or qkv.shape[2] != 3 * nhead * 64:
+        raise _lib.FarHipError(f'vit_attention_train_qkv: qkv (Z, N, 3 * nhead * 64), head dim 64 only (K23); got {tuple(qkv.shape)} '
+                               f'for {nhead} heads')
+    if qkv.dtype != torch.float32:
+        raise _lib.FarHipError(f'expected dtype {torch.float32}, got {qkv.dtype}')
+    return _VitAttentionFn.apply(nhead, True, qkv)
 
 class _LinearAttentionFn(torch.autograd.Function):
     """K5 with its HIP backward (far_linear_attention_f32 / far_linear_attention_bwd_f32)."""

@@ -1,4 +1,4 @@
-"""The 8-Point-ViT regressor of FAR (interiornetStreetlearn_8ptVit/src/model.py: ViTEss) behind its ResNet18 extractor, inference only.
+"""The 8-Point-ViT regressor of FAR (interiornetStreetlearn_8ptVit/src/model.py: ViTEss) behind its ResNet18 extractor: inference, and -- opt-in -- training.
 
 Mirrors the module / parameter structure of the reference so that a released checkpoint loads with strict=True after dropping its
 `resnet.*` / `extractor_final_conv.*` entries:
@@ -11,9 +11,17 @@ the trunk and the head model.py:171-217, 6D -> matrix tools.py:20-60.
 Kernels: K6 (LayerNorm), K9 (qkv into head planes, proj / fc2 with the residual in the epilogue, fc1), K23 (the head-dim-64 softmax
 self-attention, ops.vit_attention_planes), K2 (the CrossBlock), K15 (every Linear of the head).  No eager fallback: CPU tensors raise.
 
+Training (the reference's train.py: MSE on the translation plus MSE on the rotation output, clip_grad_norm_, AdamW) is opt-in,
+modelled on LoFTR.set_full_attention_training(): `ViTEss.set_block_training()` sets `block_training` on the trunk, its Blocks and
+their Attention modules; without it a call that needs gradients raises NotImplementedError as before.  With it a Block runs K6
+forward + backward (ops.layernorm_train), K9 forward + dgrad and K16 wgrad for qkv, proj, fc1 and fc2 (ops.linear_train, one PackCache
+per module), and K23's training forward + HIP backward on the qkv projection in place (ops.vit_attention_train_qkv: no chunk, no cat);
+GELU and the residual adds are elementwise torch ops.  The CrossBlock trains on K2's kernels; the head's two small parameter
+containers run under autograd (the package's convention for them, far_amd/_vendor.py).  `pose_loss` is the reference's loss;
+far_amd.optim (K20) is the optimizer side.  The no-grad path is the same code and the same bits whatever the switch says.
+
 Not built (each raises NotImplementedError): the extractor (torchvision's ResNet18 conv1 .. layer2 + ResidualBlock; `forward(images)`),
-training / gradients through the Blocks, dropout and drop-path (0 in every script), per-sample intrinsics, and the pooled-conv
-ablation (fusion_transformer=False).
+dropout and drop-path (0 in every script), per-sample intrinsics, and the pooled-conv ablation (fusion_transformer=False).
 
 Pair order: the reference keeps the two images of pair b in rows 2b, 2b + 1 of a (2B, N, C) tensor; this package's CrossBlock takes
 cat([img0s, img1s]).  forward_features takes and returns the reference's order and converts once, in front of the trunk (the
@@ -84,13 +92,26 @@ def loftr_gate_inputs(data):
 def _no_drop(**rates):
     for name, r in rates.items():
         if r:
-            raise NotImplementedError(f'{name}={r}: dropout / drop-path are 0 in every 8-Point-ViT script and exist in training only; '
-                                      'this package builds the inference path')
+            raise NotImplementedError(f'{name}={r}: dropout / drop-path are 0 in every 8-Point-ViT script; this package does not build '
+                                      'them')
+
+
+def pose_loss(outputs, gt_tran, gt_rot, w_tr, w_rot, losson6d=False):
+    """The reference's training loss (interiornetStreetlearn_8ptVit/train.py:308-344) on what forward_features returns:
+    w_tr mean((tran_preds - gt_tran)^2) + w_rot mean((rot_preds - gt_rot)^2); with losson6d the rotation term is on rot_preds_6d
+    and gt_rot is the (B, 6) ground truth in the same (normalised or not) units.  gt_tran: (B, 3) in the units of tran_preds;
+    gt_rot: (B, J, 3) rest poses under the ground-truth rotation.  Pure torch on the four returned tensors."""
+    tran_preds, rot_preds, _, rot_preds_6d = outputs
+    loss_tr = torch.pow(tran_preds - gt_tran, 2).mean()
+    loss_rot = torch.pow((rot_preds_6d if losson6d else rot_preds) - gt_rot, 2).mean()
+    return w_tr * loss_tr + w_rot * loss_rot
 
 
 class Attention(nn.Module):
     """vision_transformer.py:236-262: the qkv Linear on K9 straight into head planes, K23, `proj` on K9 (the Block adds the residual
-    in its epilogue).  Head dim 64 only."""
+    in its epilogue).  Head dim 64 only.  forward_train is the form with gradients (block_training)."""
+
+    block_training = False       # True: gradients run K23's training forward + HIP backward; False: a call that needs them raises
 
     def __init__(self, dim, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
         super().__init__()
@@ -111,9 +132,23 @@ class Attention(nn.Module):
         a = ops.vit_attention_planes(planes, self.num_heads)                                # (Z, N, C), heads concatenated
         return ops.linear_f16s(a, pp, residual=None if residual is None else residual.contiguous())
 
+    def forward_train(self, x):
+        """proj(attention(qkv(x))) with gradients: K9 forward + dgrad and K16 wgrad for both Linear layers, K23's training forward and
+        HIP backward on the (Z, N, 3 C) projection in place."""
+        if not self.block_training:
+            raise NotImplementedError('vit8pt.Attention: gradients through K23 (far_vit_attention_f16s) are off for this module; '
+                                      'ViTEss.set_block_training() / block_training = True turns the HIP backward on')
+        pk = self.__dict__.setdefault('_packs', ops.PackCache())
+        qkv = ops.linear_train(x, self.qkv.weight, self.qkv.bias, pk, ('train', 'qkv'))
+        a = ops.vit_attention_train_qkv(qkv, self.num_heads)
+        return ops.linear_train(a, self.proj.weight, self.proj.bias, pk, ('train', 'proj'))
+
 
 class Block(nn.Module):
-    """vision_transformer.py:265-283: x + attn(norm1(x)), then x + mlp(norm2(x)); K6, K9, K23, K9, K6, K9, K9."""
+    """vision_transformer.py:265-283: x + attn(norm1(x)), then x + mlp(norm2(x)); K6, K9, K23, K9, K6, K9, K9.  With block_training
+    a call that needs gradients runs the same operators with their backward kernels (K6, K9 + K16, K23 backward)."""
+
+    block_training = False
 
     def __init__(self, dim, num_heads, mlp_ratio=4., qkv_bias=False, drop=0., attn_drop=0., drop_path=0., act_layer=nn.GELU,
                  norm_layer=nn.LayerNorm):
@@ -126,8 +161,17 @@ class Block(nn.Module):
 
     def forward(self, x, intrinsics=None):
         if ag.needs_grad(x, self.norm1.weight):
-            raise NotImplementedError('vit8pt.Block: training / gradients through the ViT blocks are not built -- K23 '
-                                      '(far_vit_attention_f16s) has no backward; call it under torch.no_grad()')
+            if not self.block_training:
+                raise NotImplementedError('vit8pt.Block: training / gradients through the ViT blocks are off (K23, '
+                                          'far_vit_attention_f16s, runs as an inference kernel); ViTEss.set_block_training() turns the '
+                                          'HIP backward on, or call it under torch.no_grad()')
+            if not x.is_cuda:
+                raise ops._lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+            pk = self.__dict__.setdefault('_packs', ops.PackCache())
+            x = x + self.attn.forward_train(ops.layernorm_train(x.contiguous(), self.norm1))
+            hid = self.mlp.act(ops.linear_train(ops.layernorm_train(x.contiguous(), self.norm2), self.mlp.fc1.weight, self.mlp.fc1.bias,
+                                                pk, ('train', 'fc1')))
+            return x + ops.linear_train(hid, self.mlp.fc2.weight, self.mlp.fc2.bias, pk, ('train', 'fc2'))
         x = x.contiguous()
         x = self.attn(ops.layernorm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps), residual=x)
         return self.mlp(ops.layernorm(x, self.norm2.weight, self.norm2.bias, self.norm2.eps), residual=x)
@@ -138,7 +182,9 @@ class FusionTransformer(nn.Module):
     final LayerNorm.  forward takes cat([img0s, img1s]) (2B, 576, 192) and returns (2B, 70, 192), rows (2b, 2b + 1) = pair b.
 
     intrinsics: None (the plain table) or one camera's (fx, fy, cx, cy) on the 24 x 24 grid; one positional table is built per
-    distinct value and kept (both datasets have one camera)."""
+    distinct value and kept (both datasets have one camera).  With block_training gradients pass through (pos_embed included)."""
+
+    block_training = False
 
     def __init__(self, embed_dim=DIM, depth=6, num_heads=HEADS, mlp_ratio=4., qkv_bias=True, drop_rate=0., attn_drop_rate=0.,
                  drop_path_rate=0.):
@@ -164,9 +210,11 @@ class FusionTransformer(nn.Module):
 
     def forward(self, x, intrinsics=None, taps=None):
         """taps: optional list that receives every block's output (tests)."""
-        if ag.needs_grad(x, self.pos_embed):
-            raise NotImplementedError('vit8pt.FusionTransformer: training / gradients are not built (K23, far_vit_attention_f16s, '
-                                      'has no backward); call it under torch.no_grad()')
+        train = ag.needs_grad(x, self.pos_embed)
+        if train and not self.block_training:
+            raise NotImplementedError('vit8pt.FusionTransformer: training / gradients are off (K23, far_vit_attention_f16s, runs as an '
+                                      'inference kernel); ViTEss.set_block_training() turns the HIP backward on, or call it under '
+                                      'torch.no_grad()')
         if not x.is_cuda:
             raise ops._lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
         cross = self.blocks[-1]
@@ -176,6 +224,8 @@ class FusionTransformer(nn.Module):
             x = blk(x)
             if taps is not None:
                 taps.append(x)
+        if train:
+            return ops.layernorm_train(x.contiguous(), self.norm)
         return ops.layernorm(x.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps)
 
 
@@ -224,6 +274,17 @@ class ViTEss(nn.Module):
 
     update_intrinsics = staticmethod(update_intrinsics)
 
+    def set_block_training(self, on=True):
+        """Opt in to (or out of) gradients through the trunk: sets `block_training` on the FusionTransformer, its Blocks and their
+        Attention modules -- plain instance attributes, the state dict's keys do not change.  Returns self."""
+        on = bool(on)
+        ft = self.fusion_transformer
+        ft.block_training = on
+        for blk in ft.blocks:
+            if isinstance(blk, Block):
+                blk.block_training = blk.attn.block_training = on
+        return self
+
     def forward(self, images, intrinsics=None, inference=False, loftr_num_corr=None, loftr_preds=None):
         raise NotImplementedError('ViTEss.forward(images): the extractor (torchvision ResNet18 conv1 .. layer2 + ResidualBlock, '
                                   'model.py:131-163) is not built -- torchvision is not a dependency of this package.  Run it '
@@ -261,9 +322,27 @@ class ViTEss(nn.Module):
             if self.global_pose_mean is None or self.global_pose_std is None:
                 raise ValueError('use_normalized_6d needs global_pose_mean and global_pose_std')
             mean, std = self.global_pose_mean.to(dev).float(), self.global_pose_std.to(dev).float()
+        if self.use_loftr_gating and (loftr_preds is None or loftr_num_corr is None):
+            raise ValueError('use_loftr_gating needs loftr_preds (B, 4, 4) and loftr_num_corr (B,)')
+        if ag.needs_grad(feats, reg[0].weight, self.moe_predictor[0].weight if self.use_loftr_gating else None):
+            # training: the two small parameter containers under autograd (far_amd/_vendor.py; the mp3d head's forward_emm does the
+            # same) -- the same function as below, model.py:181-205; the reg0 | moe0 merge is an inference optimisation only
+            pred_reg_6d = reg(feats)
+            if self.use_loftr_gating:
+                rt = loftr_preds.to(dev).float()
+                solver_6d = torch.cat([rt[..., :3, 3], rt[..., :2, :3].reshape(B, 6)], dim=-1)
+                if self.use_normalized_6d:
+                    solver_6d = (solver_6d - mean) / std
+                ncorr = loftr_num_corr.detach().to(dev).float().reshape(B, 1) / 500
+                solver_6d = torch.cat([solver_6d, ncorr], dim=-1)
+                wt = self.moe_predictor(torch.cat([feats, pred_reg_6d, solver_6d], dim=-1))
+                pred_T = wt[..., :1] * pred_reg_6d[..., :3] + (1 - wt[..., :1]) * solver_6d[..., :3]
+                pred_R = wt[..., 1:] * pred_reg_6d[..., 3:] + (1 - wt[..., 1:]) * solver_6d[..., 3:-1]
+                pose = torch.cat([pred_T, pred_R], dim=-1)
+            else:
+                pose = pred_reg_6d
+            return self._pose_outputs(pose, mean, std)
         if self.use_loftr_gating:
-            if loftr_preds is None or loftr_num_corr is None:
-                raise ValueError('use_loftr_gating needs loftr_preds (B, 4, 4) and loftr_num_corr (B,)')
             moe = self.moe_predictor
             # the two 26880-wide first layers read the features only: one K15 launch for both (no bias yet)
             both = pk.get('reg0|moe0', [reg[0].weight, moe[0].weight],
@@ -291,6 +370,10 @@ class ViTEss(nn.Module):
             pose = torch.cat([pred_T, pred_R], dim=-1)
         else:
             pose = pred_reg_6d
+        return self._pose_outputs(pose, mean, std)
+
+    def _pose_outputs(self, pose, mean, std):
+        """model.py:206-217: the (B, 9) pose -> the four returned tensors."""
         rot_6d, tran = pose[:, 3:], pose[:, :3]
         if self.use_normalized_6d:
             rot_unnorm = rot_6d * std[3:] + mean[3:]

@@ -359,6 +359,30 @@ int far_vit_attention_f16s(const float* q, const float* k, const float* v, int Z
                            long q_row, long kv_img, long kv_head, long kv_row, int act_exp, float* out, int* overflow,
                            far_stream_t stream);
 
+/* K23 under autograd (vit_attention_f16s.hip, vit_attention_bwd_f16s.hip).
+ * far_vit_attention_train_f16s: far_vit_attention_f16s -- the same launch, the same `out` bits -- that also writes lse [Z][H][L] fp32:
+ * lse[z, h, l] = log2 sum_s 2^(log2(e) q_l . k_s / 8), the log2-domain log-sum-exp of row l's scaled scores in the units of the
+ * unscaled inputs, from which the backward recomputes the probabilities.
+ * far_vit_attention_bwd_f16s: dq, dk, dv for g = dL/dout from recomputed score tiles -- no (L, S)-sized tensor exists, no float
+ * atomics, an image's gradient bits do not depend on the batch it is computed in, results are bit-identical from run to run.  q, k, v:
+ * addressed by strides as in the forward; out, g: [Z][L][H*64] fp32 contiguous; lse: what the training forward wrote for the same q,
+ * k, v and act_exp.  Row (n, h, l) of dq is the 64 contiguous floats at dq + n dq_img + h dq_head + l dq_row, rows of dk and dv
+ * likewise with the dkv_* strides: with q = qkv, k = qkv + H*64, v = qkv + 2*H*64 (img = N 3 H 64, head = 64, row = 3 H 64) one
+ * [Z][N][3*H*64] projection is read in place, and dq, dk, dv set up the same way are written into one [Z][N][3*H*64] gradient.
+ * D = 64 only; every stride a multiple of 4, rows at least 64 apart, base pointers 16-byte aligned (else -22).  The score recompute
+ * and dp = g . v^T run on split-fp16 operands, the three output contractions on plain fp16 operands; g and ds are scaled by powers
+ * of two taken from per-image max-abs reductions on the device (no host synchronisation).  overflow |= 1 when a q / k / v / g value
+ * is beyond 65504 / 2^act_exp (q, k, v) or not finite.  ws: far_vit_attention_bwd_workspace_bytes(Z, L, S, H, D) bytes: > 0 for
+ * every valid size, 0 for D != 64 or Z = 0, linear in Z; the query needs no GPU. */
+int far_vit_attention_train_f16s(const float* q, const float* k, const float* v, int Z, int L, int S, int H, int D, long q_img,
+                                 long q_head, long q_row, long kv_img, long kv_head, long kv_row, int act_exp, float* out, float* lse,
+                                 int* overflow, far_stream_t stream);
+size_t far_vit_attention_bwd_workspace_bytes(int Z, int L, int S, int H, int D);
+int far_vit_attention_bwd_f16s(const float* q, const float* k, const float* v, const float* out, const float* lse, const float* g, int Z,
+                               int L, int S, int H, int D, long q_img, long q_head, long q_row, long kv_img, long kv_head, long kv_row,
+                               int act_exp, float* dq, float* dk, float* dv, long dq_img, long dq_head, long dq_row, long dkv_img,
+                               long dkv_head, long dkv_row, void* ws, int* overflow, far_stream_t stream);
+
 /* K22 under autograd (full_attention_f16s.hip, full_attention_bwd_f16s.hip).
  * far_full_attention_train_f16s: far_full_attention_f16s -- the same launches, the same `out` bits, the same workspace -- that also
  * writes lse [N][H][L] fp32: the log2-domain log-sum-exp of row l's scaled scores (+1e30 for a padded query row and for every row of

@@ -4,12 +4,17 @@
     B = 32 pairs (Z = 2 and 64 images), next to the fp32 torch composition of the same operator (scores materialised, softmax,
     P V) and torch's fused scaled_dot_product_attention on fp32 inputs;
   * one ViTEss.forward_features call (5 Blocks, CrossBlock, LayerNorm, head) at B = 1 and B = 32, next to the fp32 torch
-    restatement of the same model (tests/vit8pt_ref.py) on the same weights.
+    restatement of the same model (tests/vit8pt_ref.py) on the same weights;
+  * training (--legs train): K23's training forward + HIP backward (ops.vit_attention_train_qkv on one (Z, N, 3 C) projection) at
+    the same shape for Z = 2 and Z = 64, its raw forward and raw backward launches on their own (the backward / forward ratio),
+    next to fp32 torch autograd of the materialising composition and of scaled_dot_product_attention;
+  * one training iteration without the optimizer -- forward_features + pose_loss + backward with set_block_training() -- at B = 1
+    and B = 32, next to the fp32 torch restatement under autograd (tests/vit8pt_train_ref.py).
 
 Timing: HIP events around groups of launches (a group is long enough that the event resolution and the launch gaps do not decide),
 every leg warmed up first, the legs ALTERNATED round by round, medians over the rounds with the min .. max spread.  The MFMA floor
 of K23 is 3 (split products) x 4 L S H 64 Z flop at the 1.71 PFLOP/s that far_mfma_probe_f16 sustains.
-Prints a table and one JSON line.  Usage: python tools/vit8pt_time.py [--rounds N]"""
+Prints a table and one JSON line.  Usage: python tools/vit8pt_time.py [--rounds N] [--legs inference,train]"""
 import argparse
 import json
 import os
@@ -100,27 +105,130 @@ def model_case(B, rounds):
     return {'B': B, 'max_abs_diff_of_the_outputs': dev, **{name: {'median_ms': md, 'min_ms': lo, 'max_ms': hi} for name, (md, lo, hi) in r.items()}}
 
 
+def attention_train_case(B, rounds):
+    H, N, Z = 3, 576, 2 * B
+    C = H * 64
+    g = torch.Generator(device='cuda').manual_seed(B)
+    qkv = (torch.randn(Z, N, 3 * C, device='cuda', generator=g) * 1.5).requires_grad_()
+    go = torch.randn(Z, N, C, device='cuda', generator=g)
+    q4, k4, v4 = (qkv.detach()[..., t * C:(t + 1) * C].reshape(Z, N, H, 64).transpose(1, 2).contiguous().requires_grad_() for t in range(3))
+    g4 = go.reshape(Z, N, H, 64).transpose(1, 2).contiguous()
+    from far_amd.ops import attention as at
+    raw = qkv.detach()
+    views = (raw[..., :C], raw[..., C:2 * C], raw[..., 2 * C:])
+    out, lse, act_exp = at._vit_train_forward(*views, Z, N, N, H)
+    into = torch.empty_like(raw)
+
+    def through(fn, leaves):
+        def run():
+            for t in leaves:
+                t.grad = None
+            fn().backward(go if leaves[0] is qkv else g4)
+        return run
+
+    def composition():
+        a = (q4 @ k4.transpose(-2, -1)) * 0.125
+        return a.softmax(dim=-1) @ v4
+
+    def sdpa():
+        return torch.nn.functional.scaled_dot_product_attention(q4, k4, v4)
+    legs = {'k23_train_forward': lambda: at._vit_train_forward(*views, Z, N, N, H),
+            'k23_backward': lambda: ops.vit_attention_bwd(*views, out, lse, go, H, act_exp, into=into),
+            'k23_forward_backward': through(lambda: ops.vit_attention_train_qkv(qkv, H), (qkv,)),
+            'torch_fp32_composition_autograd': through(composition, (q4, k4, v4))}
+    try:                                     # a torch build without an fp32 fused path with a backward: the leg is left out
+        through(sdpa, (q4, k4, v4))()
+        legs['torch_fp32_sdpa_autograd'] = through(sdpa, (q4, k4, v4))
+    except RuntimeError as e:
+        print(f'# torch_fp32_sdpa_autograd not timed: {str(e).splitlines()[0]}')
+    r = alternate(legs, rounds)
+    legs['k23_forward_backward']()
+    legs['torch_fp32_composition_autograd']()
+    ref = torch.cat([t.grad.transpose(1, 2).reshape(Z, N, C) for t in (q4, k4, v4)], dim=-1)
+    dev = float((qkv.grad - ref).norm() / ref.norm())
+    return {'B': B, 'Z': Z, 'rel_frobenius_diff_of_dqkv_vs_composition': dev,
+            'backward_over_forward': r['k23_backward'][0] / r['k23_train_forward'][0],
+            **{name: {'median_ms': m, 'min_ms': lo, 'max_ms': hi} for name, (m, lo, hi) in r.items()}}
+
+
+def model_train_case(B, rounds):
+    from far_amd.vit8pt import ViTEss, pose_loss
+    from tests import vit8pt_inputs as vi
+    from tests import vit8pt_ref as vr
+    from tests import vit8pt_train_ref as vtr
+    ref = vr.RefViTEss(vi.vit_args())
+    inp = vi.seeded_inputs(vi.seeded_fill(ref), 1)
+    ref.pose_mean, ref.pose_std = inp['pose_mean'], inp['pose_std']
+    m = ViTEss(vi.vit_args(), inp['pose_mean'], inp['pose_std'])
+    m.load_state_dict(ref.state_dict(), strict=True)
+    m, ref = m.cuda().train().set_block_training(), vtr.from_ref(ref, torch.float32, 'cuda').train()
+    g = torch.Generator(device='cuda').manual_seed(100 + B)
+    feats = torch.randn(2 * B, 576, 192, device='cuda', generator=g)
+    gt_tran, gt_rot = torch.randn(B, 3, device='cuda', generator=g), torch.randn(B, 3, 3, device='cuda', generator=g)
+    intr = inp['intrinsics'].cuda().expand(B, 2, 4).contiguous()
+    ncorr, preds = inp['loftr_num_corr'].cuda().expand(B).contiguous(), inp['loftr_preds'].cuda().expand(B, 4, 4).contiguous()
+
+    def step(model, k):
+        def run():
+            model.zero_grad(set_to_none=True)
+            loss = pose_loss(model.forward_features(feats, k, ncorr, preds), gt_tran, gt_rot, 1.0, 1.0)
+            loss.backward()
+            return loss
+        return run
+    ours, theirs = step(m, intr), step(ref, vi.VIT_INTRINSICS)
+    r = alternate({'far_amd': ours, 'torch_fp32_restatement': theirs}, rounds, target_ms=60.0)
+    dl = abs(float(ours().detach()) - float(theirs().detach()))
+    name = 'fusion_transformer.blocks.0.attn.qkv.weight'
+    ga, gb = dict(m.named_parameters())[name].grad, dict(ref.named_parameters())[name].grad
+    return {'B': B, 'abs_diff_of_the_loss': dl, 'rel_frobenius_diff_of_block0_dqkv_weight': float((ga - gb).norm() / gb.norm()),
+            **{nm: {'median_ms': md, 'min_ms': lo, 'max_ms': hi} for nm, (md, lo, hi) in r.items()}}
+
+
+def main_train(a, res, fmt):
+    res['attention_train'], res['train_iteration'] = [], []
+    for B in (1, 32):
+        c = attention_train_case(B, a.rounds)
+        res['attention_train'].append(c)
+        print(f'# attention training L = S = 576, H = 3, D = 64, Z = {c["Z"]}; backward / forward = {c["backward_over_forward"]:.2f} '
+              f'(K22: 2.4-3.0); rel Frobenius difference of dqkv against the fp32 composition {c["rel_frobenius_diff_of_dqkv_vs_composition"]:.2e}')
+        for leg in (n for n in ('k23_train_forward', 'k23_backward', 'k23_forward_backward', 'torch_fp32_composition_autograd',
+                                'torch_fp32_sdpa_autograd') if n in c):
+            print(f'  {leg:34s} {fmt(c[leg])}' + (f'   x{c[leg]["median_ms"] / c["k23_forward_backward"]["median_ms"]:.2f} of K23 forward + backward'
+                                                if leg.startswith('torch') else ''))
+    for B in (1, 32):
+        c = model_train_case(B, a.rounds)
+        res['train_iteration'].append(c)
+        print(f'# forward_features + pose_loss + backward B = {B} (depth 6, gating, normalized 6d); |loss difference| {c["abs_diff_of_the_loss"]:.2e}, '
+              f'block 0 dqkv.weight rel Frobenius difference {c["rel_frobenius_diff_of_block0_dqkv_weight"]:.2e}')
+        for leg in ('far_amd', 'torch_fp32_restatement'):
+            print(f'  {leg:34s} {fmt(c[leg])}' + (f'   x{c[leg]["median_ms"] / c["far_amd"]["median_ms"]:.2f} of far_amd' if leg != 'far_amd' else ''))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=15)
+    ap.add_argument('--legs', default='inference,train', help='comma-separated: inference, train')
     a = ap.parse_args()
+    which = set(a.legs.split(','))
     if not torch.cuda.is_available():
         raise SystemExit('vit8pt_time needs a GPU: nothing is timed without one')
     res = {'tool': 'vit8pt_time', 'device': torch.cuda.get_device_name(), 'rounds': a.rounds, 'attention': [], 'forward_features': []}
     fmt = lambda d: f'{d["median_ms"]:9.4f} ms  ({d["min_ms"]:.4f} .. {d["max_ms"]:.4f})'
-    for B in (1, 32):
+    for B in (1, 32) if 'inference' in which else ():
         c = attention_case(B, a.rounds)
         res['attention'].append(c)
         print(f'# attention L = S = 576, H = 3, D = 64, B = {B} (Z = {c["Z"]}, {c["workgroups"]} workgroups), MFMA floor {c["mfma_floor_ms"]:.4f} ms')
         for leg in (n for n in ('k23', 'torch_fp32_composition', 'torch_fp32_sdpa') if n in c):
             print(f'  {leg:26s} {fmt(c[leg])}' + (f'   x{c[leg]["median_ms"] / c["k23"]["median_ms"]:.2f} of K23' if leg != 'k23' else
                                                 f'   {c["mfma_floor_ms"] / c[leg]["median_ms"]:.1%} of the MFMA floor'))
-    for B in (1, 32):
+    for B in (1, 32) if 'inference' in which else ():
         c = model_case(B, a.rounds)
         res['forward_features'].append(c)
         print(f'# forward_features B = {B} (depth 6, gating, normalized 6d); max |output difference| {c["max_abs_diff_of_the_outputs"]:.2e}')
         for leg in ('far_amd', 'torch_fp32_restatement'):
             print(f'  {leg:26s} {fmt(c[leg])}' + (f'   x{c[leg]["median_ms"] / c["far_amd"]["median_ms"]:.2f} of far_amd' if leg != 'far_amd' else ''))
+    if 'train' in which:
+        main_train(a, res, fmt)
     print(json.dumps(res))
 
 
