@@ -1,4 +1,4 @@
-"""far_amd.ops.conv: K9 / K17 / K10 convolutions (inference + training forms), BatchNorm K19, FPN upsample-add K8, affine epilogues K7 (one family of the torch-tensor front ends for the C ABI in include/far_hip.h; far_amd/ops/__init__.py
+"""far_amd.ops.conv: K9 / K17 / K10 convolutions (inference + training forms), the extractor's K24 / K25 / K26, BatchNorm K19, FPN upsample-add K8, affine epilogues K7 (one family of the torch-tensor front ends for the C ABI in include/far_hip.h; far_amd/ops/__init__.py
 re-exports everything under the flat far_amd.ops namespace the rest of the package uses)."""
 import ctypes
 import os
@@ -8,7 +8,7 @@ import torch
 
 from .. import _lib, flags
 from ._base import _ACT, _p, _same_layout, _stream, _written, activation_exponent_value, grad_scale, overflow_flag
-from .packs import PackedConv, WINO_MIN_ACT_EXP, WINO_MIN_PIXELS
+from .packs import PackedConv, PackedConvValid, PackedStemRGB, WINO_MIN_ACT_EXP, WINO_MIN_PIXELS
 
 
 class _ConvF16sFn(torch.autograd.Function):
@@ -497,3 +497,76 @@ def stem_train(img, weight):
     if not img.is_cuda:
         raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
     return _StemFn.apply(img, weight)
+
+def conv_valid(x, pack, residual=None, act='none'):
+    """K24.  x (N, H, W, Cin) fp32 contiguous -> act(conv5x5_valid(x) * scale + shift (+ residual)) as (N, H - 4, W - 4, Cout) for a
+    PackedConvValid; act 'none' or 'relu'; residual in the output's layout.  Takes part in the activation-range guard as K9 does."""
+    lib = _lib.load()
+    if not isinstance(pack, PackedConvValid):
+        raise _lib.FarHipError('conv_valid takes a PackedConvValid')
+    if x.dim() != 4 or x.shape[-1] != pack.Cin:
+        raise _lib.FarHipError(f'conv_valid: input of shape {tuple(x.shape)}, weights expect (N, H, W, {pack.Cin})')
+    N, H, W, Cin = x.shape
+    k = pack.ksize
+    if H < k or W < k:
+        raise _lib.FarHipError(f'conv_valid: a {H} x {W} input is smaller than the {k} x {k} kernel')
+    if act not in ('none', 'relu'):
+        raise _lib.FarHipError("conv_valid: act is 'none' or 'relu'")
+    y = torch.empty(N, H - k + 1, W - k + 1, pack.Cout, dtype=torch.float32, device=x.device)
+    if residual is not None and (tuple(residual.shape) != tuple(y.shape) or not residual.is_contiguous()):
+        raise _lib.FarHipError(f'conv_valid: `residual` must be a contiguous {tuple(y.shape)} tensor')
+    rc = lib.far_conv_valid_f16s(_p(x, torch.float32), _p(pack.packed), _p(pack.scale), _p(pack.shift, torch.float32), _p(residual, torch.float32),
+                                 _p(y), N, H, W, Cin, pack.Cout, k, _ACT[act], activation_exponent_value(), overflow_flag(x.device).data_ptr(),
+                                 _stream())
+    _lib.check(rc, 'far_conv_valid_f16s')
+    return y
+
+_RESIZE_TABLES = {}
+
+def resize_tables(H, W, device, size=224):
+    """The source row / column of every destination row / column of F.interpolate(x, size=size) (nearest) for an (H, W) fp32 image on
+    `device`, as two int32 device vectors -- taken from torch's own interpolate of two index images, once per (H, W, device), so that
+    K25 reads exactly the pixels torch would."""
+    device = torch.device(device)
+    key = (int(H), int(W), str(device), int(size))
+    t = _RESIZE_TABLES.get(key)
+    if t is None:
+        F = torch.nn.functional
+        rows = F.interpolate(torch.arange(H, dtype=torch.float32, device=device).view(1, 1, H, 1).expand(1, 1, H, W).contiguous(), size=size)[0, 0]
+        cols = F.interpolate(torch.arange(W, dtype=torch.float32, device=device).view(1, 1, 1, W).expand(1, 1, H, W).contiguous(), size=size)[0, 0]
+        r, c = rows[:, 0].to(torch.int32).contiguous(), cols[0, :].to(torch.int32).contiguous()
+        ok = (bool((rows == rows[:, :1]).all()) and bool((cols == cols[:1, :]).all()) and 0 <= int(r.min()) and int(r.max()) < H
+              and 0 <= int(c.min()) and int(c.max()) < W)
+        if not ok:
+            raise _lib.FarHipError(f'resize_tables: the nearest-neighbour resize of a {H} x {W} image is not a row / column gather')
+        t = _RESIZE_TABLES[key] = (r, c)
+    return t
+
+def stem_rgb(images, pack):
+    """K25.  images (N, 3, H, W) fp32 contiguous on the GPU, values 0 .. 255 in the channel order the reference takes -> relu(bn1(conv1(
+    F.interpolate(normalise(flip(images)), size=224)))) as NHWC (N, 112, 112, 64) for a PackedStemRGB; `images` is only read."""
+    lib = _lib.load()
+    if not isinstance(pack, PackedStemRGB):
+        raise _lib.FarHipError('stem_rgb takes a PackedStemRGB')
+    if not images.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] < 1 or images.shape[3] < 1:
+        raise _lib.FarHipError(f'stem_rgb expects (N, 3, H, W) images, got {tuple(images.shape)}')
+    N, _, H, W = images.shape
+    rows, cols = resize_tables(H, W, images.device)
+    y = torch.empty(N, 112, 112, 64, dtype=torch.float32, device=images.device)
+    rc = lib.far_stem_rgb_f16s(_p(images, torch.float32), N, H, W, _p(rows, torch.int32), _p(cols, torch.int32), _p(pack.packed), _p(pack.scale),
+                               _p(pack.shift), _p(y), _stream())
+    _lib.check(rc, 'far_stem_rgb_f16s')
+    return y
+
+def maxpool3x3s2(x):
+    """K26.  F.max_pool2d(x, 3, stride=2, padding=1) for NHWC x (N, H, W, C) fp32 contiguous, C % 4 == 0 -> (N, (H - 1) // 2 + 1,
+    (W - 1) // 2 + 1, C); exact."""
+    lib = _lib.load()
+    if x.dim() != 4 or x.shape[-1] % 4 or x.shape[1] < 1 or x.shape[2] < 1:
+        raise _lib.FarHipError(f'maxpool3x3s2 expects NHWC (N, H, W, C) with C % 4 == 0, got {tuple(x.shape)}')
+    N, H, W, C = x.shape
+    y = torch.empty(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, dtype=torch.float32, device=x.device)
+    _lib.check(lib.far_maxpool3x3s2_nhwc_f32(_p(x, torch.float32), N, H, W, C, _p(y), _stream()), 'far_maxpool3x3s2_nhwc_f32')
+    return y

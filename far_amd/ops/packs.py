@@ -149,6 +149,77 @@ class PackedWino:
         self._w = w
         return self
 
+class PackedConvValid:
+    """Weights of one K x K unpadded stride-1 convolution (K = 5) in K24's packed split-fp16 image, plus the folded epilogue vectors:
+    the same constructor meaning as PackedConv (scale / shift: the inference BatchNorm as a per-channel affine map, a convolution
+    bias folded into shift by the caller)."""
+
+    stride, split = 1, True
+
+    def __init__(self, weight, scale=None, shift=None):
+        lib = _lib.load()
+        w = weight.detach()
+        if w.dim() != 4 or w.shape[2] != w.shape[3]:
+            raise _lib.FarHipError(f'K24 takes a (Cout, Cin, k, k) weight, got {tuple(w.shape)}')
+        if not w.is_cuda:
+            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+        w = w.contiguous().float()
+        self.Cout, self.Cin, self.ksize = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+        nbytes = int(lib.far_conv_valid_packed_bytes(self.Cin, self.Cout, self.ksize))
+        if nbytes == 0:
+            raise _lib.FarHipError(f'K24 (far_conv_valid_f16s) covers 5x5 kernels with Cin and Cout multiples of 32, got a weight of shape '
+                                   f'{tuple(w.shape)}')
+        self.packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+        self.pack_scale = torch.empty(2, dtype=torch.float32, device=w.device)       # { 2^w_exp, 2^-(w_exp + 4) }
+        self._base = None if scale is None else scale.detach().float().contiguous()
+        self.scale = torch.empty(self.Cout, dtype=torch.float32, device=w.device)
+        self.shift = None if shift is None else shift.detach().float().contiguous()
+        self._wshape = tuple(w.shape)
+        self.refresh(w)
+
+    def refresh(self, weight):
+        """(Re-)packs the image from `weight` into the same buffers: two launches, no allocation, no host read."""
+        lib = _lib.load()
+        w = weight.detach()
+        if tuple(w.shape) != self._wshape or w.dtype != torch.float32 or not w.is_contiguous() or w.device != self.packed.device:
+            raise _lib.FarHipError('PackedConvValid.refresh: the weight changed shape, dtype, layout or device')
+        _lib.check(lib.far_weight_scale_f32(_p(w, torch.float32), w.numel(), _p(self.pack_scale), _stream()), 'far_weight_scale_f32')
+        rc = lib.far_conv_valid_pack_f32(_p(w), self.Cin, self.Cout, self.ksize, _p(self.pack_scale), _p(self.packed),
+                                         _p(self._base) if self._base is not None else None, _p(self.scale), _stream())
+        _lib.check(rc, 'far_conv_valid_pack_f32')
+        self._w = w
+        return self
+
+class PackedStemRGB:
+    """The (64, 3, 7, 7) weight of the extractor's stem in K25's split-fp16 fragments, plus the folded BatchNorm (scale, shift)."""
+
+    def __init__(self, weight, scale, shift):
+        lib = _lib.load()
+        w = weight.detach()
+        if tuple(w.shape) != (64, 3, 7, 7):
+            raise _lib.FarHipError(f'K25 (far_stem_rgb_f16s) takes a (64, 3, 7, 7) weight, got {tuple(w.shape)}')
+        if not w.is_cuda:
+            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+        w = w.contiguous().float()
+        self.Cout = 64
+        self.packed = torch.empty(int(lib.far_stem_rgb_packed_bytes()), dtype=torch.uint8, device=w.device)
+        self.pack_scale = torch.empty(2, dtype=torch.float32, device=w.device)
+        self._base = scale.detach().float().contiguous()
+        self.scale = torch.empty(64, dtype=torch.float32, device=w.device)
+        self.shift = shift.detach().float().contiguous()
+        self.refresh(w)
+
+    def refresh(self, weight):
+        lib = _lib.load()
+        w = weight.detach()
+        if tuple(w.shape) != (64, 3, 7, 7) or w.dtype != torch.float32 or not w.is_contiguous() or w.device != self.packed.device:
+            raise _lib.FarHipError('PackedStemRGB.refresh: the weight changed shape, dtype, layout or device')
+        _lib.check(lib.far_weight_scale_f32(_p(w, torch.float32), w.numel(), _p(self.pack_scale), _stream()), 'far_weight_scale_f32')
+        rc = lib.far_stem_rgb_pack_f32(_p(w), _p(self.pack_scale), _p(self.packed), _p(self._base), _p(self.scale), _stream())
+        _lib.check(rc, 'far_stem_rgb_pack_f32')
+        self._w = w
+        return self
+
 WINO_MIN_ACT_EXP = 0        # K17 splits its operands unscaled (|a| <= 16376): used while the activation exponent is >= 0
 
 WINO_MIN_PIXELS = 1024      # per image; below, a 16x16-output workgroup tile is mostly padding

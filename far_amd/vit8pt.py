@@ -1,7 +1,8 @@
-"""The 8-Point-ViT regressor of FAR (interiornetStreetlearn_8ptVit/src/model.py: ViTEss) behind its ResNet18 extractor: inference, and -- opt-in -- training.
+"""The 8-Point-ViT regressor of FAR (interiornetStreetlearn_8ptVit/src/model.py: ViTEss): inference from extractor features or -- opt-in --
+from images, and -- opt-in -- training of the trunk and the head.
 
-Mirrors the module / parameter structure of the reference so that a released checkpoint loads with strict=True after dropping its
-`resnet.*` / `extractor_final_conv.*` entries:
+Mirrors the module / parameter structure of the reference so that a released checkpoint loads with strict=True after
+reference_state_dict(sd) dropped its `resnet.*` / `extractor_final_conv.*` entries:
     fusion_transformer.pos_embed, fusion_transformer.blocks.{i}.{norm1, attn.qkv, attn.proj, norm2, mlp.fc1, mlp.fc2},
     fusion_transformer.blocks.{depth-1}.{norm1, cross_attn.qkv, cross_attn.proj_fundamental, norm2, mlp.*}, fusion_transformer.norm,
     pose_regressor.{0, 2, 4}, moe_predictor.{0, 2, 4}
@@ -10,6 +11,17 @@ the trunk and the head model.py:171-217, 6D -> matrix tools.py:20-60.
 
 Kernels: K6 (LayerNorm), K9 (qkv into head planes, proj / fc2 with the residual in the epilogue, fc1), K23 (the head-dim-64 softmax
 self-attention, ops.vit_attention_planes), K2 (the CrossBlock), K15 (every Linear of the head).  No eager fallback: CPU tensors raise.
+
+The extractor (model.py:56-60, :131-163; modules/extractor.py:5-65) is opt-in: `ViTEss(args, mean, std, extractor=True)` adds
+    resnet.{conv1, bn1, layer1.{0, 1}, layer2.{0, 1}} (torchvision's ResNet18 front under its names; layer2.0 with downsample.{0, 1}),
+    extractor_final_conv.{conv1, conv2, norm1, norm2, norm3, downsample.{0, 1}} (downsample.1 IS norm3, as in the reference)
+as nn.Conv2d / nn.BatchNorm2d modules -- reference_state_dict(sd, extractor=True) then drops only resnet.layer3.* / layer4.* -- and
+`forward(images)` / `extract_features(images)` run it in 14 launches: K25 (ops.stem_rgb: channel flip, / 255, normalisation, nearest
+resize to 224, conv1, bn1, relu), K26 (ops.maxpool3x3s2), K9 / K17 (ops.conv_nhwc: layer1, layer2, extractor_final_conv.conv1) and
+K24 (ops.conv_valid: the two 5x5 unpadded convolutions with the block's add and ReLUs).  It is inference-only and FROZEN, which the
+reference's is not (it fine-tunes these layers): requires_grad False on its parameters, running statistics in every BatchNorm
+whatever .train() says, detached features under set_block_training(); an extractor parameter with requires_grad=True raises when
+gradients are enabled.  Without the keyword nothing changes: no such submodules, and forward(images) raises as before.
 
 Training (the reference's train.py: MSE on the translation plus MSE on the rotation output, clip_grad_norm_, AdamW) is opt-in,
 modelled on LoFTR.set_full_attention_training(): `ViTEss.set_block_training()` sets `block_training` on the trunk, its Blocks and
@@ -20,8 +32,8 @@ GELU and the residual adds are elementwise torch ops.  The CrossBlock trains on 
 containers run under autograd (the package's convention for them, far_amd/_vendor.py).  `pose_loss` is the reference's loss;
 far_amd.optim (K20) is the optimizer side.  The no-grad path is the same code and the same bits whatever the switch says.
 
-Not built (each raises NotImplementedError): the extractor (torchvision's ResNet18 conv1 .. layer2 + ResidualBlock; `forward(images)`),
-dropout and drop-path (0 in every script), per-sample intrinsics, and the pooled-conv ablation (fusion_transformer=False).
+Not built (each raises NotImplementedError): extractor training, dropout and drop-path (0 in every script), per-sample intrinsics, and
+the pooled-conv ablation (fusion_transformer=False).
 
 Pair order: the reference keeps the two images of pair b in rows 2b, 2b + 1 of a (2B, N, C) tensor; this package's CrossBlock takes
 cat([img0s, img1s]).  forward_features takes and returns the reference's order and converts once, in front of the trunk (the
@@ -229,6 +241,66 @@ class FusionTransformer(nn.Module):
         return ops.layernorm(x.contiguous(), self.norm.weight, self.norm.bias, self.norm.eps)
 
 
+def reference_state_dict(sd, extractor=False):
+    """A released checkpoint's state dict -> the entries a ViTEss of this package loads with strict=True.  extractor=True (a model
+    built with the keyword): only `resnet.layer3.*` / `resnet.layer4.*` go -- the layers model.py:147-152 never runs (`resnet.fc` is an
+    Identity: it has no entries); otherwise every `resnet.*` / `extractor_final_conv.*` entry goes."""
+    drop = ('resnet.layer3.', 'resnet.layer4.') if extractor else ('resnet.', 'extractor_final_conv.')
+    return {k: v for k, v in sd.items() if not k.startswith(drop)}
+
+
+class _BasicBlock(nn.Module):
+    """torchvision's BasicBlock under its parameter names (conv1, bn1, conv2, bn2, downsample.{0, 1}); run by Extractor on K9 / K17."""
+
+    def __init__(self, cin, cout, stride):
+        super().__init__()
+        self.conv1 = nn.Conv2d(cin, cout, 3, stride, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(cout)
+        self.conv2 = nn.Conv2d(cout, cout, 3, 1, 1, bias=False)
+        self.bn2 = nn.BatchNorm2d(cout)
+        self.downsample = None
+        if stride != 1 or cin != cout:
+            self.downsample = nn.Sequential(nn.Conv2d(cin, cout, 1, stride, bias=False), nn.BatchNorm2d(cout))
+
+
+class _ResNetFront(nn.Module):
+    """The layers of torchvision's ResNet18 that model.py:147-152 runs: conv1, bn1, (relu, maxpool), layer1, layer2."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.layer1 = nn.Sequential(_BasicBlock(64, 64, 1), _BasicBlock(64, 64, 1))
+        self.layer2 = nn.Sequential(_BasicBlock(64, 128, 2), _BasicBlock(128, 128, 1))
+
+
+class _FinalConv(nn.Module):
+    """extractor.py:5-65 as model.py:60 builds it: ResidualBlock(128, 192, 'batch', kernel_size=5); downsample.1 IS norm3."""
+
+    def __init__(self):
+        super().__init__()
+        self.conv1 = nn.Conv2d(128, DIM, 3, padding=1)
+        self.conv2 = nn.Conv2d(DIM, DIM, 5)
+        self.norm1 = nn.BatchNorm2d(DIM)
+        self.norm2 = nn.BatchNorm2d(DIM)
+        self.norm3 = nn.BatchNorm2d(DIM)
+        self.downsample = nn.Sequential(nn.Conv2d(128, DIM, 5), self.norm3)
+
+
+def _fold(conv, bn):
+    """(scale, shift) of bn(conv(.)) with the RUNNING statistics as a per-channel affine map behind the bias-free convolution:
+    scale = gamma / sqrt(var + eps), shift = beta - mean scale + scale bias; folded in float64, returned in fp32."""
+    scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+    shift = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+    if conv.bias is not None:
+        shift = shift + scale * conv.bias.detach().double()
+    return scale.float(), shift.float()
+
+
+def _fold_tensors(conv, bn):
+    return [t for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+
+
 def _one_camera(intrinsics):
     """(B, 2, 4) -> the (fx, fy, cx, cy) every frame of the batch shares (host floats)."""
     k = intrinsics.detach().float().cpu()
@@ -244,12 +316,19 @@ def _one_camera(intrinsics):
 
 
 class ViTEss(nn.Module):
-    """model.py:38-217 without the extractor.  args: fusion_transformer (must be True), transformer_depth, fc_hidden_size, pool_size
+    """model.py:38-217; the extractor only with extractor=True (module docstring).  args: fusion_transformer (must be True), transformer_depth, fc_hidden_size, pool_size
     (read, unused on this path), use_loftr_gating, use_normalized_6d, T_pose (J, 3).  global_pose_mean / global_pose_std: (9,)
     tensors, needed with use_normalized_6d (plain attributes as in the reference: not part of the state dict)."""
 
-    def __init__(self, args, global_pose_mean=None, global_pose_std=None):
+    def __init__(self, args, global_pose_mean=None, global_pose_std=None, extractor=False):
         super().__init__()
+        self.has_extractor = bool(extractor)
+        if self.has_extractor:
+            # model.py:58-60 under the reference's names; inference-only and frozen in this package (the reference fine-tunes them)
+            self.resnet = _ResNetFront()
+            self.extractor_final_conv = _FinalConv()
+            self.resnet.requires_grad_(False)
+            self.extractor_final_conv.requires_grad_(False)
         self.total_num_features = DIM
         self.feature_resolution = GRID
         self.pose_size = 9
@@ -285,11 +364,66 @@ class ViTEss(nn.Module):
                 blk.block_training = blk.attn.block_training = on
         return self
 
+    def _no_extractor(self):
+        return NotImplementedError('ViTEss.forward(images): the extractor (torchvision ResNet18 conv1 .. layer2 + ResidualBlock, '
+                                   'model.py:131-163) is not built -- torchvision is not a dependency of this package.  Run it '
+                                   'elsewhere and call forward_features(features, intrinsics, loftr_num_corr, loftr_preds) with its '
+                                   '(2B, 576, 192) output and update_intrinsics(images.shape, intrinsics)')
+
     def forward(self, images, intrinsics=None, inference=False, loftr_num_corr=None, loftr_preds=None):
-        raise NotImplementedError('ViTEss.forward(images): the extractor (torchvision ResNet18 conv1 .. layer2 + ResidualBlock, '
-                                  'model.py:131-163) is not built -- torchvision is not a dependency of this package.  Run it '
-                                  'elsewhere and call forward_features(features, intrinsics, loftr_num_corr, loftr_preds) with its '
-                                  '(2B, 576, 192) output and update_intrinsics(images.shape, intrinsics)')
+        """model.py:165-217 from images (a model built with extractor=True): images (B, 2, 3, H, W) fp32 on the GPU, values 0 .. 255
+        in the channel order the reference takes, left unmodified; intrinsics: None or (B, 2, 4) [fx, fy, cx, cy] AT THE IMAGE SIZE.
+        The same bits as forward_features(*extract_features(images, intrinsics), loftr_num_corr, loftr_preds)."""
+        if not self.has_extractor:
+            raise self._no_extractor()
+        return self.forward_features(*self.extract_features(images, intrinsics), loftr_num_corr, loftr_preds)
+
+    def _block(self, pk, name, blk, x):
+        """One BasicBlock on K9 / K17: relu(bn1(conv1(x))), then relu(bn2(conv2(.)) + shortcut) with the add and the ReLU in conv2's
+        epilogue; the 1x1 stride-2 shortcut reads x[:, ::2, ::2] in place (in_stride = 2)."""
+        st = blk.conv1.stride[0]
+        fold = lambda conv, bn, **kw: (lambda: ops.PackedConv(conv.weight, *_fold(conv, bn), **kw))
+        p1 = pk.get(name + '.conv1', _fold_tensors(blk.conv1, blk.bn1), fold(blk.conv1, blk.bn1, stride=st))
+        p2 = pk.get(name + '.conv2', _fold_tensors(blk.conv2, blk.bn2), fold(blk.conv2, blk.bn2))
+        y = ops.conv_nhwc(x, p1, act='relu')
+        if blk.downsample is not None:
+            pd = pk.get(name + '.downsample', _fold_tensors(blk.downsample[0], blk.downsample[1]), fold(blk.downsample[0], blk.downsample[1]))
+            x = ops.conv_nhwc(x, pd, in_stride=st)
+        return ops.conv_nhwc(y, p2, residual=x, act='relu')
+
+    def extract_features(self, images, intrinsics=None):
+        """model.py:131-163: images (B, 2, 3, H, W) fp32 on the GPU, 0 .. 255 -> (features (2B, 576, 192) with rows (2b, 2b + 1) = pair
+        b, intrinsics on the 24 x 24 grid (update_intrinsics with the ORIGINAL image size; None stays None)).  14 launches: K25 (flip,
+        normalisation, resize to 224, conv1, bn1, relu), K26 (maxpool), K9 / K17 (layer1, layer2, extractor_final_conv.conv1), K24
+        (the two 5x5 convolutions with the block's add and ReLUs).  BatchNorm uses its running statistics whatever .train() says;
+        the extractor is frozen: the features carry no gradient.  `images` is only read."""
+        if not self.has_extractor:
+            raise self._no_extractor()
+        if not torch.is_tensor(images) or images.dim() != 5 or tuple(images.shape[1:3]) != (2, 3):
+            raise ValueError(f'images: (B, 2, 3, H, W), got {tuple(images.shape) if torch.is_tensor(images) else type(images)}')
+        if torch.is_grad_enabled() and any(p.requires_grad for m in (self.resnet, self.extractor_final_conv) for p in m.parameters()):
+            raise NotImplementedError('ViTEss: training the extractor (resnet.* / extractor_final_conv.*) is not built -- its kernels are '
+                                      'inference kernels and its BatchNorm layers use running statistics; keep its parameters at '
+                                      'requires_grad=False (the constructor sets that) or call it under torch.no_grad()')
+        if not images.is_cuda:
+            raise ops._lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+        grid_intrinsics = None if intrinsics is None else update_intrinsics(images.shape, intrinsics)
+        pk = self.__dict__.setdefault('_extractor_packs', ops.PackCache())
+        rn, fc = self.resnet, self.extractor_final_conv
+        with torch.no_grad():
+            stem = pk.get('stem', _fold_tensors(rn.conv1, rn.bn1), lambda: ops.PackedStemRGB(rn.conv1.weight, *_fold(rn.conv1, rn.bn1)))
+            x = ops.maxpool3x3s2(ops.stem_rgb(images.detach().flatten(0, 1).contiguous(), stem))          # (2B, 56, 56, 64) NHWC
+            for lname, layer in (('layer1', rn.layer1), ('layer2', rn.layer2)):
+                for i, blk in enumerate(layer):
+                    x = self._block(pk, f'{lname}.{i}', blk, x)                                          # -> (2B, 28, 28, 128)
+            p1 = pk.get('final.conv1', _fold_tensors(fc.conv1, fc.norm1), lambda: ops.PackedConv(fc.conv1.weight, *_fold(fc.conv1, fc.norm1)))
+            p2 = pk.get('final.conv2', _fold_tensors(fc.conv2, fc.norm2), lambda: ops.PackedConvValid(fc.conv2.weight, *_fold(fc.conv2, fc.norm2)))
+            pd = pk.get('final.downsample', _fold_tensors(fc.downsample[0], fc.norm3),
+                        lambda: ops.PackedConvValid(fc.downsample[0].weight, *_fold(fc.downsample[0], fc.norm3)))
+            y = ops.conv_valid(ops.conv_nhwc(x, p1, act='relu'), p2, act='relu')                        # extractor.py:53-54
+            x = ops.conv_valid(x, pd, residual=y, act='relu')                                            # :56-57, :65 -> (2B, 24, 24, 192)
+        # model.py:156-161: (2B, 192, 576) permuted to (2B, 576, 192) is the NHWC tensor itself; the channel cut [:, :192] is a no-op
+        return x.reshape(x.shape[0], self.num_patches, DIM), grid_intrinsics
 
     def trunk(self, features, intrinsics=None, taps=None):
         """(2B, 576, 192) extractor output in the reference's pair order -> the (2B, 70, 192) normalised features (model.py:171-180).

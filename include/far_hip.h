@@ -30,7 +30,7 @@ typedef struct ihipStream_t* far_stream_t; /* == hipStream_t */
 
 /* ABI version of this header; bumped when a signature changes (2: activation exponent / overflow flag of K9, K13, K14; 3: the
  * far_wino_* / far_conv3x3_wino_f32 entry points, 16 tuning keys; 4: far_upsample2x_bwd_f32, far_fine_scatter_det_f32, far_bn_train_*, far_adamw_*; 5: far_linear_kv_f16s, far_linear_q_apply_f16s,
- * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way, and so were far_grad_norm_workspace_bytes, far_grad_norm_f32, far_grad_clip_scale_f32 and far_adam_step_f32, and the five far_bn_sync_*_f32 entry points).  far_amd/_lib.py refuses a library whose version differs. */
+ * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way, and so were far_grad_norm_workspace_bytes, far_grad_norm_f32, far_grad_clip_scale_f32 and far_adam_step_f32, and the five far_bn_sync_*_f32 entry points, and the far_conv_valid_* / far_stem_rgb_* / far_maxpool3x3s2_nhwc_f32 entry points of K24-K26).  far_amd/_lib.py refuses a library whose version differs. */
 int far_abi_version(void);
 /* Id of the sources the library was built from: sha256/16 over far_amd/csrc/* and the compiler flags (far_amd/build.py
  * source_id()).  far_amd/_lib.py refuses a library whose id differs from the sources it sits next to. */
@@ -771,6 +771,42 @@ int far_stem7x7_nhwc_f32(const float* img, const float* w, const float* scale, c
 long far_stem7x7_wgrad_ws_bytes(int N, int H, int W, int Cout);
 int far_stem7x7_wgrad_f32(const float* img, const float* dy, int N, int H, int W, int Cout, void* ws, long ws_bytes, float* dw,
                           far_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K24  5x5 unpadded ('valid') stride-1 convolution, NHWC fp32, split-fp16 MFMA, K9's epilogue
+ * replaces interiornetStreetlearn_8ptVit/src/modules/extractor.py:11, :46-47 (conv2 and downsample.0 of the ResidualBlock
+ *   model.py:60 builds with kernel_size 5), with norm2 / norm3 folded and the block's add + ReLU (:54, :65) in the epilogue
+ * y[n][oy][ox][co] = act(scale[co] 2^(4 - act_exp) sum_{ky,kx,ci} x[n][oy+ky][ox+kx][ci] W[co][ci][ky][kx] + shift[co] (+ res))
+ * x [N][H][W][Cin], res / y [N][H-4][W-4][Cout] fp32 NHWC contiguous, x 16-byte aligned; H, W >= 5; Cin, Cout multiples of 32
+ * (far_conv_valid_packed_bytes returns 0 for anything else, the other two -22).  far_conv_valid_pack_f32: w [Cout][Cin][5][5]
+ * (torch layout) times pack_scale[0] (far_weight_scale_f32's two device floats) into `packed`, and scale_vec[co] = base_scale[co]
+ * (1 when NULL) * pack_scale[1], the vector the launch takes as `scale`.  shift may be NULL; act: 0 none, 1 ReLU (NaN kept);
+ * act_exp / overflow as far_conv_nhwc_f32.  Deterministic; image n's output does not depend on N.  y aliases neither x nor res.
+ * --------------------------------------------------------------------------------------------------- */
+size_t far_conv_valid_packed_bytes(int Cin, int Cout, int ksize);
+int far_conv_valid_pack_f32(const float* w, int Cin, int Cout, int ksize, const float* pack_scale, void* packed, const float* base_scale,
+                            float* scale_vec, far_stream_t stream);
+int far_conv_valid_f16s(const float* x, const void* packed, const float* scale, const float* shift, const float* res, float* y, long N,
+                        int H, int W, int Cin, int Cout, int ksize, int act, int act_exp, int* overflow, far_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * K25  RGB stem of the 8-Point-ViT's extractor, one launch; K26  max-pool 3x3 stride 2 pad 1 (NHWC, exact)
+ * far_stem_rgb_f16s replaces interiornetStreetlearn_8ptVit/src/model.py:135-138 (channel flip, / 255, (x - mean) / std), :145
+ *   (F.interpolate(size=224), nearest) and :147-149 (resnet.conv1 7x7 stride 2 pad 3, bn1 folded, relu):
+ *   y[n][oy][ox][co] = relu(scale[co] sum_{c,ky,kx} X[n][c][2 oy+ky-3][2 ox+kx-3] w[co][c][ky][kx] + shift[co]),
+ *   X[n][c][i][j] = (img[n][2-c][rowidx[i]][colidx[j]] / 255 - mean[c]) / std[c] inside the 224 x 224 grid, 0 outside (the padding
+ *   is zero in normalised space).  img [N][3][H][W] fp32, 0 .. 255, not modified; rowidx / colidx [224] int32 device tables with
+ *   entries in [0, H) / [0, W) (taken from torch's own interpolate by the caller); y [N][112][112][64] NHWC.
+ *   far_stem_rgb_pack_f32: w [64][3][7][7] -> `packed` (far_stem_rgb_packed_bytes() bytes, 16-byte aligned) and scale_vec as K24's.
+ * far_maxpool3x3s2_nhwc_f32 replaces model.py:150 (resnet.maxpool): x [N][H][W][C] -> y [N][(H-1)/2+1][(W-1)/2+1][C], C % 4 == 0,
+ *   16-byte aligned; the padding counts as -inf, a NaN stays a NaN.
+ * --------------------------------------------------------------------------------------------------- */
+size_t far_stem_rgb_packed_bytes(void);
+int far_stem_rgb_pack_f32(const float* w, const float* pack_scale, void* packed, const float* base_scale, float* scale_vec,
+                          far_stream_t stream);
+int far_stem_rgb_f16s(const float* img, long N, int H, int W, const int* rowidx, const int* colidx, const void* packed,
+                      const float* scale, const float* shift, float* y, far_stream_t stream);
+int far_maxpool3x3s2_nhwc_f32(const float* x, long N, int H, int W, int C, float* y, far_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * K11  per-pair arithmetic between the solver and the regression head (one launch each)
