@@ -15,7 +15,9 @@
 //     dq: rows = queries (x-operand q, dP-operand A, weight u, row normaliser), columns = keys (k, v~, v, column normaliser)
 //     dk: rows = keys    (k, v~, v, column normaliser),                        columns = queries (q, A, u, row normaliser)
 // Arithmetic: plain fp16 operands, fp32 accumulation (gradient-grade, ~1e-3; measured in tests/test_train_kernels_gpu.py
-// against float64 autograd).  A, B, u, v arrive pre-scaled by the caller so that max |A|, |B| ~ 1.
+// against float64 autograd) -- except the recomputed SCORES, which take split-fp16 q, k (hi.hi + hi.lo + lo.hi, as the forward
+// does): a score sits in an exponent, and plain fp16 q, k cost |s| 2^-11 there, which at |q|, |k| ~ 2 randn already put dq, dk
+// at 0.6 - 1.4e-2 per problem (tests/test_emm_parity_gpu.py).  A, B, u, v arrive pre-scaled by the caller so that max |A|, |B| ~ 1.
 #include "common.h"
 #include <algorithm>
 
@@ -34,13 +36,14 @@ constexpr int YROW = 176;             // bytes per row of a dP-operand plane: 80
 constexpr int TROW = 80;              // bytes per channel row of a transposed x tile: 32 positions + 16 B pad
 constexpr int XT_TILE = D * TROW;     // 5 KiB
 constexpr int X_SLOT = 5 * 1024, Y_SLOT = 6 * 1024, T_SLOT = 5 * 1024;      // LDS slots (DMA granule 1 KiB per wave)
-constexpr int STAGE = X_SLOT + Y_SLOT + T_SLOT + 256;                      // + 32 (weight, normaliser) pairs
+constexpr int STAGE = 2 * X_SLOT + Y_SLOT + T_SLOT + 256;                  // x hi, y, x^T, x lo, + 32 (weight, normaliser) pairs
 constexpr float PRE = 16.0f;
 constexpr float HUGE_F = 1.0e30f;
 
-// x [Z][N][W] fp32 (row stride `ld` floats) -> [Z][Np][rowbytes] fp16 rows (value * 2^4, W..Wp-1 and rows >= N zero)
+// x [Z][N][W] fp32 (row stride `ld` floats) -> [Z][Np][rowbytes] fp16 rows (value * 2^4, W..Wp-1 and rows >= N zero);
+// out_lo (or null): the same rows of the split's low parts, fp16(value * 2^4 - hi)
 __global__ void k2b_prep_rows(const float* __restrict__ x, int Z, int N, int Np, int W, int ld, int Wp, int rowbytes,
-                              unsigned char* __restrict__ out) {
+                              unsigned char* __restrict__ out, unsigned char* __restrict__ out_lo) {
     const int nslot = Wp / 8;
     const long total = (long)Z * Np * nslot;
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
@@ -48,13 +51,16 @@ __global__ void k2b_prep_rows(const float* __restrict__ x, int Z, int N, int Np,
         const long row = t / nslot;
         const int i = (int)(row % Np);
         const long z = row / Np;
-        f16x8 v;
+        f16x8 v, vl;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int c = 8 * slot + e;
-            v[e] = (i < N && c < W) ? (_Float16)(x[((size_t)z * N + i) * ld + c] * PRE) : (_Float16)0.f;
+            const float a = (i < N && c < W) ? x[((size_t)z * N + i) * ld + c] * PRE : 0.f;
+            v[e] = (_Float16)a;
+            vl[e] = (_Float16)(a - (float)v[e]);
         }
         *reinterpret_cast<f16x8*>(out + (size_t)row * rowbytes + slot * 16) = v;
+        if (out_lo) *reinterpret_cast<f16x8*>(out_lo + (size_t)row * rowbytes + slot * 16) = vl;
     }
 }
 
@@ -104,8 +110,10 @@ __device__ __forceinline__ void dma_lin(unsigned char* lds, const unsigned char*
 }
 
 // out[z][row][64] = coef * sum_col ds[row][col] * Xcol[col][:]
-__global__ __launch_bounds__(256, 2) void k2_bwd(const unsigned char* __restrict__ xr, const unsigned char* __restrict__ yr,
+__global__ __launch_bounds__(256, 2) void k2_bwd(const unsigned char* __restrict__ xr, const unsigned char* __restrict__ xrl,
+                                                 const unsigned char* __restrict__ yr,
                                                  const float2* __restrict__ wlr, const unsigned char* __restrict__ xc,
+                                                 const unsigned char* __restrict__ xcl,
                                                  const unsigned char* __restrict__ yc, const unsigned char* __restrict__ xct,
                                                  const float2* __restrict__ wlc, int Z, int N, int Np, float c1, float dps,
                                                  float coef, float* __restrict__ out) {
@@ -114,12 +122,15 @@ __global__ __launch_bounds__(256, 2) void k2_bwd(const unsigned char* __restrict
     int z, Ib;
     tile_coords(Np / 128, Z, z, Ib);
     const int irow = Ib * 128 + 32 * wave + l31;
-    f16x8 xf[4], yf[5];
+    f16x8 xf[4], xfl[4], yf[5];
     {
         const unsigned char* px = xr + ((size_t)z * Np + irow) * XROW;
+        const unsigned char* pxl = xrl + ((size_t)z * Np + irow) * XROW;
         const unsigned char* py = yr + ((size_t)z * Np + irow) * YROW;
 #pragma unroll
         for (int s = 0; s < 4; ++s) xf[s] = *reinterpret_cast<const f16x8*>(px + (2 * s + h) * 16);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) xfl[s] = *reinterpret_cast<const f16x8*>(pxl + (2 * s + h) * 16);
 #pragma unroll
         for (int s = 0; s < 5; ++s) yf[s] = *reinterpret_cast<const f16x8*>(py + (2 * s + h) * 16);
     }
@@ -135,7 +146,8 @@ __global__ __launch_bounds__(256, 2) void k2_bwd(const unsigned char* __restrict
         dma_lin(base, xc + ((size_t)z * Np + (size_t)jt * KT) * XROW, KT * XROW, tid, wave);
         dma_lin(base + X_SLOT, yc + ((size_t)z * Np + (size_t)jt * KT) * YROW, KT * YROW, tid, wave);
         dma_lin(base + X_SLOT + Y_SLOT, xct + ((size_t)z * ntile + jt) * XT_TILE, XT_TILE, tid, wave);
-        if (tid < KT) reinterpret_cast<float2*>(base + X_SLOT + Y_SLOT + T_SLOT)[tid] = wlc[(size_t)z * Np + jt * KT + tid];
+        dma_lin(base + X_SLOT + Y_SLOT + T_SLOT, xcl + ((size_t)z * Np + (size_t)jt * KT) * XROW, KT * XROW, tid, wave);
+        if (tid < KT) reinterpret_cast<float2*>(base + 2 * X_SLOT + Y_SLOT + T_SLOT)[tid] = wlc[(size_t)z * Np + jt * KT + tid];
     };
     request(0, 0);
     for (int jt = 0; jt < ntile; ++jt) {
@@ -146,14 +158,20 @@ __global__ __launch_bounds__(256, 2) void k2_bwd(const unsigned char* __restrict
         const unsigned char* xs = lds + st * STAGE;
         const unsigned char* ys = xs + X_SLOT;
         const unsigned char* ts = ys + Y_SLOT;
-        const float2* cw = reinterpret_cast<const float2*>(ts + T_SLOT);
+        const unsigned char* xls = ts + T_SLOT;
+        const float2* cw = reinterpret_cast<const float2*>(xls + X_SLOT);
         // scores and dP, transposed: D[m = column of the tile][n = this lane's row]
         f32x16 sc, dp;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { sc[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
-        for (int s = 0; s < 4; ++s)
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(xs + l31 * XROW + (2 * s + h) * 16), xf[s], sc, 0, 0, 0);
+        for (int s = 0; s < 4; ++s) {                                   // split-fp16 scores: hi.hi + hi.lo + lo.hi
+            const f16x8 ch = *reinterpret_cast<const f16x8*>(xs + l31 * XROW + (2 * s + h) * 16);
+            const f16x8 cl = *reinterpret_cast<const f16x8*>(xls + l31 * XROW + (2 * s + h) * 16);
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, xf[s], sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, xfl[s], sc, 0, 0, 0);
+            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, xf[s], sc, 0, 0, 0);
+        }
 #pragma unroll
         for (int s = 0; s < 5; ++s)
             dp = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<const f16x8*>(ys + l31 * YROW + (2 * s + h) * 16), yf[s], dp, 0, 0, 0);
@@ -165,7 +183,11 @@ __global__ __launch_bounds__(256, 2) void k2_bwd(const unsigned char* __restrict
             const float x = sc[r] * c1;
             const float er = __builtin_amdgcn_exp2f(x - wl.y), ec = __builtin_amdgcn_exp2f(x - c.y);
             const float g = 2.0f * (er * ec) * (dp[r] * dps) - er * wl.x - ec * c.x;
-            gp[r >> 3][r & 7] = (_Float16)g;
+            // A zero-padded token scores 0, not -inf: its own normaliser (+huge) zeroes one exponential, but the other is
+            // 2^(0 - lse) of a REAL token -- with every real score below 0 that is large (beyond 2^128 it is inf, and
+            // inf * 0 = NaN; from 2^16 / |weight| on the fp16 ds is inf, and inf times the zero operand row is NaN in
+            // every real row of the tile).  ds of a padded row or column is 0.
+            gp[r >> 3][r & 7] = (wl.y >= 0.5f * HUGE_F || c.y >= 0.5f * HUGE_F) ? (_Float16)0.f : (_Float16)g;
         }
         // out[row][channel] += ds[row][col] * Xcol[col][channel]
 #pragma unroll
@@ -187,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void k2_bwd(const unsigned char* __restrict
 
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 struct Ws {
-    unsigned char *qx, *kx, *ay, *vy, *qt, *kt;
+    unsigned char *qx, *kx, *qxl, *kxl, *ay, *vy, *qt, *kt;
     float2 *wlq, *wlk;
     size_t bytes;
 };
@@ -198,6 +220,7 @@ inline Ws carve(void* base, int Z, int N) {
     auto take = [&](size_t n) { unsigned char* r = p ? p + o : nullptr; o += align256(n + 1024); return r; };   // + DMA slack
     Ws w;
     w.qx = take((size_t)Z * Np * XROW); w.kx = take((size_t)Z * Np * XROW);
+    w.qxl = take((size_t)Z * Np * XROW); w.kxl = take((size_t)Z * Np * XROW);
     w.ay = take((size_t)Z * Np * YROW); w.vy = take((size_t)Z * Np * YROW);
     w.qt = take((size_t)Z * (Np / KT) * XT_TILE); w.kt = take((size_t)Z * (Np / KT) * XT_TILE);
     w.wlq = (float2*)take((size_t)Z * Np * 8); w.wlk = (float2*)take((size_t)Z * Np * 8);
@@ -227,10 +250,10 @@ int far_emm_bwd_f16(const float* q, const float* k, const float* vt, const float
     const Ws w = carve(ws, Z, N);
     const int Np = (N + 127) / 128 * 128;
     auto gridp = [](long n) { long g = (n + 255) / 256; return (unsigned)(g < 65536 ? (g > 0 ? g : 1) : 65536); };
-    hipLaunchKernelGGL(k2b_prep_rows, dim3(gridp((long)Z * Np * 8)), dim3(256), 0, stream, q, Z, N, Np, D, D, D, XROW, w.qx);
-    hipLaunchKernelGGL(k2b_prep_rows, dim3(gridp((long)Z * Np * 8)), dim3(256), 0, stream, k, Z, N, Np, D, D, D, XROW, w.kx);
-    hipLaunchKernelGGL(k2b_prep_rows, dim3(gridp((long)Z * Np * 10)), dim3(256), 0, stream, A, Z, N, Np, DV, DV, DVP, YROW, w.ay);
-    hipLaunchKernelGGL(k2b_prep_rows, dim3(gridp((long)Z * Np * 10)), dim3(256), 0, stream, vt, Z, N, Np, DV, DV, DVP, YROW, w.vy);
+    hipLaunchKernelGGL(k2b_prep_rows, dim3(gridp((long)Z * Np * 8)), dim3(256), 0, stream, q, Z, N, Np, D, D, D, XROW, w.qx, w.qxl);
+    hipLaunchKernelGGL(k2b_prep_rows, dim3(gridp((long)Z * Np * 8)), dim3(256), 0, stream, k, Z, N, Np, D, D, D, XROW, w.kx, w.kxl);
+    hipLaunchKernelGGL(k2b_prep_rows, dim3(gridp((long)Z * Np * 10)), dim3(256), 0, stream, A, Z, N, Np, DV, DV, DVP, YROW, w.ay, (unsigned char*)nullptr);
+    hipLaunchKernelGGL(k2b_prep_rows, dim3(gridp((long)Z * Np * 10)), dim3(256), 0, stream, vt, Z, N, Np, DV, DV, DVP, YROW, w.vy, (unsigned char*)nullptr);
     hipLaunchKernelGGL(k2b_prep_t, dim3(gridp((long)Z * (Np / KT) * D * 4)), dim3(256), 0, stream, q, Z, N, Np, w.qt);
     hipLaunchKernelGGL(k2b_prep_t, dim3(gridp((long)Z * (Np / KT) * D * 4)), dim3(256), 0, stream, k, Z, N, Np, w.kt);
     hipLaunchKernelGGL(k2b_side, dim3(gridp((long)Z * Np)), dim3(256), 0, stream, u, (const float2*)rowstat, Z, N, Np, w.wlq);
@@ -241,8 +264,8 @@ int far_emm_bwd_f16(const float* q, const float* k, const float* vt, const float
     const float dps = 1.0f / (PRE * PRE);                               // dP per unit of the pre-scaled dot
     const float coef = scale / PRE;                                     // ds Xcol / 2^4, times the score scale
     const dim3 grid((unsigned)(Np / 128) * Z);
-    hipLaunchKernelGGL(k2_bwd, grid, dim3(256), smem, stream, w.qx, w.ay, w.wlq, w.kx, w.vy, w.kt, w.wlk, Z, N, Np, c1, dps, coef, dq);
-    hipLaunchKernelGGL(k2_bwd, grid, dim3(256), smem, stream, w.kx, w.vy, w.wlk, w.qx, w.ay, w.qt, w.wlq, Z, N, Np, c1, dps, coef, dk);
+    hipLaunchKernelGGL(k2_bwd, grid, dim3(256), smem, stream, w.qx, w.qxl, w.ay, w.wlq, w.kx, w.kxl, w.vy, w.kt, w.wlk, Z, N, Np, c1, dps, coef, dq);
+    hipLaunchKernelGGL(k2_bwd, grid, dim3(256), smem, stream, w.kx, w.kxl, w.vy, w.wlk, w.qx, w.qxl, w.ay, w.qt, w.wlq, Z, N, Np, c1, dps, coef, dk);
     return far_check_launch();
 }
 
