@@ -35,18 +35,9 @@ NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 PACKED_FP32_FILES = {'conv_wino_f16s.hip'}
 
 
-class _PerFile(dict):
-    def get(self, name, default=None):
-        return [] if name in PACKED_FP32_FILES else NO_PACKED_FP32
-
-    def __contains__(self, name):
-        return name not in PACKED_FP32_FILES
-
-    def items(self):
-        return [('*', NO_PACKED_FP32)] + [(f, []) for f in sorted(PACKED_FP32_FILES)]
-
-
-PER_FILE_FLAGS = _PerFile()
+def per_file_flags(name):
+    """The flags the file `name` of csrc/ is compiled with on top of FLAGS."""
+    return [] if name in PACKED_FP32_FILES else NO_PACKED_FP32
 
 
 def flags_skip_asm_check():
@@ -79,7 +70,7 @@ def source_id():
     Compiled into the library (far_build_id()); _lib.load() recomputes it from the sources next to the library and refuses a
     library built from other sources -- the .so travels outside git, this is what ties it to the tree it is loaded from."""
     files = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(('.hip', '.h', '.inc'))]
-    per_file = ' '.join(f'{k}:{" ".join(v)}' for k, v in sorted(PER_FILE_FLAGS.items()))
+    per_file = ' '.join(f'{n}:{" ".join(per_file_flags(n))}' for n in sorted(os.path.basename(s) for s in sources()))
     return _digest(files, ' '.join(BASE_FLAGS + EXTRA_FLAGS) + ' | ' + per_file)[:16]
 
 
@@ -321,7 +312,7 @@ def build(force=False, verbose=True):
         obj = os.path.join(LIBDIR, os.path.basename(src)[:-4] + '.o')
         objs.append(obj)
         is_abi = os.path.basename(src) == 'abi.hip'
-        flags = FLAGS + PER_FILE_FLAGS.get(os.path.basename(src), []) + ([f'-DFAR_BUILD_ID="{bid}"'] if is_abi else [])   # abi.hip carries the id: it recompiles with every change
+        flags = FLAGS + per_file_flags(os.path.basename(src)) + ([f'-DFAR_BUILD_ID="{bid}"'] if is_abi else [])   # abi.hip carries the id: it recompiles with every change
         want = _digest([src] + hdrs, ' '.join(flags).replace(CSRC, '<csrc>'))
         side = obj + '.hash'
         have = open(side).read().strip() if os.path.exists(side) and os.path.exists(obj) else None
@@ -336,7 +327,7 @@ def build(force=False, verbose=True):
                                              stderr=subprocess.DEVNULL))
             # (a per-file -target-feature also reaches the HOST pass of hipcc, which answers "not a recognized feature for this target
             # (ignoring feature)": filtered from its stderr, everything else is passed through)
-            quiet = os.path.basename(src) in PER_FILE_FLAGS
+            quiet = bool(per_file_flags(os.path.basename(src)))
             procs.append((src, subprocess.Popen(cmd, stderr=subprocess.PIPE if quiet else None, text=quiet or None), side, want, chk))
     for src, p, side, want, chk in procs:
         if p.stderr is not None:

@@ -67,8 +67,8 @@ __device__ __forceinline__ void stagger_priority_by_wave_slot(int enable) {
 // Hardware places block b on XCD b % 8 (observed, speed only).  All nI row blocks of one problem re-read the same
 // column-side operand, so they are steered to ONE XCD's L2: measured HBM/fabric fetch of k_match_f32 at batch 32 was
 // 22x the algorithmic bytes with the naive (Ib fastest) order.  Falls back to the plain order when Z % 8 != 0.
-__device__ __forceinline__ void tile_coords(int nI, int Z, int& z, int& Ib) {
-    const int id = blockIdx.x;
+// tile_coords_of: the same for block `id` of nI * Z (a kernel whose grid holds several such ranges, one per split of another axis).
+__device__ __forceinline__ void tile_coords_of(int id, int nI, int Z, int& z, int& Ib) {
     if ((Z & 7) == 0) {
         const int xcd = id & 7, li = id >> 3;
         z = xcd + 8 * (li / nI);
@@ -78,6 +78,7 @@ __device__ __forceinline__ void tile_coords(int nI, int Z, int& z, int& Ib) {
         Ib = id - z * nI;
     }
 }
+__device__ __forceinline__ void tile_coords(int nI, int Z, int& z, int& Ib) { tile_coords_of(blockIdx.x, nI, Z, z, Ib); }
 
 // x / d for a loop-invariant divisor d, given r = 1.0f / d (IEEE).  q = fl(x r); e = fma(-d, q, x); q' = fma(e, r, q)
 // is the correctly rounded quotient (Markstein) except for divisors whose significand is all ones; 3 instructions

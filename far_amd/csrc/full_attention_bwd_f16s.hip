@@ -9,12 +9,12 @@
 //   k_bwd<KEYS = false>  dq: a workgroup owns 128 query rows (a lane ONE query, as in the forward) and walks the keys in tiles of 64.
 //   k_bwd<KEYS = true>   dk, dv: a workgroup owns 128 keys (a lane ONE key) and walks the queries in tiles of 64; dk and dv come from
 //            the same recomputed tile.
-// One template is both kernels: the owned side's two operands (q, g | k, v) sit in registers as the B operands of the two first
-// products, the walked side's tile (k, v | q, g) is staged through LDS exactly like the forward's k tile (fp32 loads of the NEXT tile in
-// flight during the MFMAs, split into fp16 (hi, lo) planes, XOR-swizzled 16-byte slots), plus its transpose in the k-order of the
-// accumulator registers for the output products.
-//   scores   x = A1 . X on 32x32x16 f16 MFMAs, hi.hi + hi.lo + lo.hi around the forward's activation exponent: p = 2^(x c1 - lse2)
-//            agrees with the saved statistic (a plain-fp16 recompute would be off by percent at |score| ~ 60).
+// One template is both kernels, on the backward recipe of attention_f16s.h (read its header first): the owned side's two operands
+// (q, g | k, v) sit in registers as the B operands of the two first products, the walked side's tile (k, v | q, g) is staged through
+// LDS exactly like the forward's k tile (fp32 loads of the NEXT tile in flight during the MFMAs, XOR-swizzled 16-byte slots), plus
+// its transpose for the output products.
+//   scores   x = A1 . X, split operands around the forward's activation exponent: p = 2^(x c1 - lse2) agrees with the saved
+//            statistic (a plain-fp16 recompute would be off by percent at |score| ~ 60).
 //   dp       A2 . Y the same way (split operands): dp - delta cancels, plain fp16 g and v would cost 1e-3 on dq and dk.
 //   outputs  ds and p go from the accumulator registers into the next MFMA as plain fp16 A operands (the forward's P V step), against
 //            the transposed hi plane of k (dq), q (dk) and g (dv).
@@ -23,17 +23,11 @@
 // scaled back by exact powers of two.  They are per IMAGE: an image's bits do not depend on the rest of the batch.
 // Masks: a masked key takes no part (p selected to 0: dk = dv = exact 0 there, its k / v values are never read); a padded query row
 // carries lse2 = +1e30 (p = 0) and g read as 0: dq = exact 0 there; an image without a valid key has lse2 = +1e30 everywhere.
-// Short owned side: the walked axis is split across workgroups (the forward's plan), partial sums go to the workspace and
+// Short owned side: the walked axis is split across workgroups (split_plan, as the forward), partial sums go to the workspace and
 // k_bwd_combine adds them in split order.  No float atomics, no data handed between the workgroups of one launch.
-#include "common.h"
+#include "attention_f16s.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float LSE_NONE = 1.0e30f;      // row statistic of a row without softmax (padded query / no valid key): p = 2^(x - 1e30) = 0
-constexpr int P_EXP = 14;                // p in [0, 1] enters the dv product as p 2^14
-constexpr int G_EXP = 12;                // max |g| 2^ge in [2^12, 2^13)
 
 template <int D_, int NCT_, int WAVES_, bool KEYS_>
 struct Cfg {
@@ -69,43 +63,6 @@ struct Args {
     int N, L, S, H, nI, nsplit, tps, act_exp;
     float pre, c1, c;
 };
-
-__device__ __forceinline__ void split8(const float (&x)[8], float pre, f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; e += 2) {
-        f16x2 h2, l2;
-        split2(f32x2{x[e], x[e + 1]} * f32x2{pre, pre}, h2, l2);
-        hi[e] = h2.x; hi[e + 1] = h2.y;
-        lo[e] = l2.x; lo[e + 1] = l2.y;
-    }
-}
-
-__device__ __forceinline__ f16x8 round8(const float (&x)[8], float pre) {
-    f16x8 y;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) y[e] = (_Float16)(x[e] * pre);
-    return y;
-}
-
-__device__ __forceinline__ void load8(const float* p, float (&x)[8]) {
-    const float4 u = *reinterpret_cast<const float4*>(p);
-    const float4 w = *reinterpret_cast<const float4*>(p + 4);
-    x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w; x[4] = w.x; x[5] = w.y; x[6] = w.z; x[7] = w.w;
-}
-
-// The image's two exponents from the bits k_prep left: g 2^ge has its maximum in [2^12, 2^13); with |v| 2^act_exp < 2^ev,
-// |ds| <= 2 D max|g 2^ge| max|v 2^act_exp| < 2^(14 + log2 D + ev), so ds 2^eds < 2^15.  A non-finite maximum (flagged by k_prep)
-// and an all-zero image get harmless exponents.
-__device__ __forceinline__ void image_exponents(const unsigned* scal, int n, int act_exp, int D, int& ge, int& eds) {
-    const unsigned gb = scal[2 * n], vb = scal[2 * n + 1];
-    ge = G_EXP - ((int)(gb >> 23) - 127);
-    int ev = (int)(vb >> 23) - 127 + 1 + act_exp;
-    eds = 1 - (D == 32 ? 5 : 4) - ev;
-    if (gb >= 0x7f800000u) ge = 0;
-    if (vb >= 0x7f800000u) eds = 0;
-    ge = ge < -100 ? -100 : (ge > 100 ? 100 : ge);
-    eds = eds < -60 ? -60 : (eds > 60 ? 60 : eds);
-}
 
 // ---- delta, the per-image maxima and the range guard: one wave per token (query rows first, then key rows), four per workgroup
 __global__ __launch_bounds__(256) void k_prep(Args a, int D) {
@@ -188,12 +145,10 @@ struct Staged {
 #pragma unroll
         for (int ci = 0; ci < C::VCH; ++ci) {
             const int c = tid + ci * C::NT;
-            const int d = c & 31, g = c >> 5;                       // g = 4 ct + 2 u + h: the slot of MFMA (ct, u), half-wave h
-            // position e of the slot holds row 32 ct + 16 u + 4 h + (e < 4 ? e : e + 4): accumulator registers 8 u .. 8 u + 7
-            const int kbase = 32 * (g >> 2) + 16 * ((g >> 1) & 1) + 4 * (g & 1);
+            const int d = c & 31, g = c >> 5;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int j = j0 + kbase + (e < 4 ? e : e + 4);
+                const int j = tplane_row(j0, g, e);
                 const bool ok = c < 32 * C::VS && d < C::D && j < Wn && (!wm || wm[j]);
                 t1[ci][e] = ok ? b1[(size_t)j * Cst + d] : 0.f;
                 if (C::KEYS) t2[ci][e] = ok ? b2[(size_t)j * Cst + d] : 0.f;
@@ -253,16 +208,9 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_bwd(Args a) {
     // block -> (split, image-head z, row block Ib), as in the forward
     const int Z = a.N * a.H;
     const int per = a.nI * Z;
-    const int sp = blockIdx.x / per, id = blockIdx.x - sp * per;
+    const int sp = blockIdx.x / per;
     int z, Ib;
-    if ((Z & 7) == 0) {
-        const int xcd = id & 7, li = id >> 3;
-        z = xcd + 8 * (li / a.nI);
-        Ib = li % a.nI;
-    } else {
-        z = id / a.nI;
-        Ib = id - z * a.nI;
-    }
+    tile_coords_of(blockIdx.x - sp * per, a.nI, Z, z, Ib);
     const int n = z / a.H, hh = z - n * a.H;
     const int Cst = a.H * D;
     const int Rn = KEYS ? a.S : a.L;       // owned axis
@@ -273,7 +221,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_bwd(Args a) {
     const bool ook = irow < Rn && (!om || om[(size_t)n * Rn + irow]);
 
     int ge, eds;
-    image_exponents(a.scal, n, a.act_exp, D, ge, eds);
+    image_exponents<D == 32 ? 5 : 4>(a.scal, n, a.act_exp, ge, eds);
     const float gpre = ldexpf(1.0f, ge);
     const float dsmul = ldexpf(1.0f, eds);
     const int dexp = ge + a.act_exp;                       // dp = (g 2^ge) . (v 2^act_exp): delta joins it at that scale
@@ -322,22 +270,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_bwd(Args a) {
         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[ct][r] = dpa[ct][r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < QS; ++s) {
-            f16x8 ch[NCT], cl[NCT];
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                const int off = C::a_off(32 * ct + l31, 2 * s + h);
-                ch[ct] = *reinterpret_cast<const f16x8*>(lds + off);
-                cl[ct] = *reinterpret_cast<const f16x8*>(lds + C::A_PLANE + off);
-            }
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], xh[s], acc[ct], 0, 0, 0);
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], xl[s], acc[ct], 0, 0, 0);
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[ct], xh[s], acc[ct], 0, 0, 0);
-        }
+        score_tile<C::a_off, C::A_PLANE>(acc, lds, l31, h, xh, xl);
+        // the same for dp, written out: with both products through the call the D = 32 one-wave dq form changes its register count
 #pragma unroll
         for (int s = 0; s < QS; ++s) {
             f16x8 ch[NCT], cl[NCT];
@@ -384,7 +318,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_bwd(Args a) {
                     const bool ok = KEYS ? ook : (((kv[ct] >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0);
                     p = ok ? p : 0.f;                                          // a masked key is selected out, whatever the score was
                     dsh[e] = (_Float16)(p * ((dpa[ct][r] - dd[e]) * dsmul));
-                    if (KEYS) ph[e] = (_Float16)(p * (float)(1 << P_EXP));
+                    if (KEYS) ph[e] = (_Float16)(p * (float)(1 << P_EXP_BWD));
                 }
                 const int off = C::t_off(l31, 4 * ct + 2 * u + h);
                 o1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(dsh, *reinterpret_cast<const f16x8*>(lds + C::OFF_T1 + off), o1, 0, 0, 0);
@@ -397,7 +331,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_bwd(Args a) {
 
     // ---- store: the lane holds channel d = l31 of owned rows i0 + mfma32_row(r, h).  ds carried 2^(ge + act_exp + eds), the
     // transposed q | k plane 2^act_exp; p 2^14 and g 2^ge
-    const int e1 = -(ge + 2 * a.act_exp + eds), e2 = -(P_EXP + ge);
+    const int e1 = -(ge + 2 * a.act_exp + eds), e2 = -(P_EXP_BWD + ge);
     float* const d1 = KEYS ? a.dk : a.dq;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -440,41 +374,16 @@ __global__ __launch_bounds__(256) void k_bwd_combine(const float* p1, const floa
     if (p2) d2[o] = s2;
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// How a launch is cut: `own` rows in blocks of 128 (32: the one-wave form), `walk` rows in tiles of 64 (32); the walked axis is split
-// when an image alone would start fewer than 64 workgroups -- the forward's rule.  A function of (L, S, H) only.
-struct Plan {
-    int nI, ntile, nsplit, tps;
-};
-inline Plan plan(int own, int walk, int H, bool small) {
-    Plan p;
-    const int rows = small ? 32 : 128, kt = small ? 32 : 64;
-    p.nI = (own + rows - 1) / rows;
-    p.ntile = (walk + kt - 1) / kt;
-    int ns = 1;
-    const long wg = (long)H * p.nI;
-    if (!small && wg < 64 && p.ntile >= 8) {
-        ns = (int)(64 / wg);
-        if (ns > p.ntile / 4) ns = p.ntile / 4;
-        if (ns > 8) ns = 8;
-        if (ns < 1) ns = 1;
-    }
-    p.tps = (p.ntile + ns - 1) / ns;
-    p.nsplit = (p.ntile + p.tps - 1) / p.tps;        // no empty split
-    return p;
-}
-
 struct Layout {
     bool small;
-    Plan pq, pk;
+    SplitPlan pq, pk;          // dq: owns L, walks S; dk / dv: owns S, walks L
     size_t off_delta, off_pq, off_pk, off_pv, bytes;
 };
 inline Layout layout(int N, int L, int S, int H, int D) {
     Layout w;
-    w.small = L <= 32 && S <= 32;
-    w.pq = plan(L, S, H, w.small);
-    w.pk = plan(S, L, H, w.small);
+    w.small = L <= 32 && S <= 32;          // both axes are walked: the one-wave form needs both short
+    w.pq = split_plan(L, S, H, w.small);
+    w.pk = split_plan(S, L, H, w.small);
     size_t o = align256((size_t)N * 2 * 4);
     w.off_delta = o; o += align256((size_t)N * H * L * 4);
     w.off_pq = o; if (w.pq.nsplit > 1) o += align256((size_t)N * H * w.pq.nsplit * L * D * 4);

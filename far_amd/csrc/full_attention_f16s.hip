@@ -4,38 +4,27 @@
 //   out[n, l, h, :] = sum_s softmax_s(q[n,l,h,:] . k[n,s,h,:] / sqrt(D)) v[n,s,h,:]
 // q (N, L, H D), k, v (N, S, H D), out (N, L, H D): fp32, contiguous raw projections with the heads concatenated (K5's layout).
 // The (N, L, S, H) score tensor of the reference never exists: one workgroup owns 128 query rows of one (image, head) -- 32 per
-// wave -- and walks the keys in tiles of 64 with an online softmax, as K2's k_pv does (emm_bilinear_f16s.hip):
+// wave -- and walks the keys in tiles of 64 with the forward recipe of attention_f16s.h (read its header first):
 //   stage    the tile's k and v rows are read as fp32 (the NEXT tile's loads are in flight while this one is computed), scaled by
-//            2^act_exp, split into fp16 (hi, lo) pairs and written to LDS: k as [key][D] rows with XOR-swizzled 16-byte slots,
-//            v transposed to [d][keys] with the keys of each group of 32 permuted into the k-order in which the score
-//            accumulators hold P.  There is no preparation launch and no operand workspace: a tile costs a thread 16 splits,
-//            against 32 exponentials.  Masked keys and keys past S are written as zeros and counted out in a 64-bit validity word.
-//   scores   S^T tile D[m = key][n = query] = k . q on 32x32x16 f16 MFMAs, hi.hi + hi.lo + lo.hi, fp32 accumulation: a lane owns ONE
-//            query, its 32 keys sit in the accumulator registers of the two half-waves.
-//   softmax  log2 domain.  The row reference R = ceil(running maximum) is an INTEGER, so a change rescales the running sum and the
-//            output accumulators by an exact power of two (v_ldexp; rare after the first tiles: behind a wave-uniform test).
-//            p = 2^(x - R + 15) in (2^14, 2^15] at the maximum: ONE exponential per score; an invalid key is selected to p = 0.
-//   P V      p is split straight from the accumulator registers (they are the A operand's k-order by construction) and
-//            multiplied with the v^T tile: out^T... D[m = query][n = d], again three MFMAs per product.
+//            2^act_exp, split and written to LDS: k as [key][D] rows with XOR-swizzled 16-byte slots, v transposed to [d][keys].
+//            There is no preparation launch and no operand workspace: a tile costs a thread 16 splits, against 32 exponentials.
+//            Masked keys and keys past S are written as zeros and counted out in a 64-bit validity word.
+//   scores   S^T tile D[m = key][n = query] = k . q: a lane owns ONE query, its 32 keys sit in the accumulator registers of the two
+//            half-waves.  A rescale of the row reference is rare after the first tiles: behind a wave-uniform test.  An invalid key
+//            is selected to p = 0.
+//   P V      p is split straight from the accumulator registers and multiplied with the v^T tile: D[m = query][n = d], again
+//            three MFMAs per product.
 //   store    out = acc / rowsum 2^-act_exp; a padded query row, and every row of an image without a valid key, is exact zero.
 // Sequences of at most 32 keys (the fine level's 25-token windows) run the same code as one wave per (image, head) and a
 // single 32-key tile: a 64-key tile and four waves would spend three quarters of their MFMAs on padding.
 // Few workgroups per image (short L, long S): the key axis is split across workgroups, the partial (R, rowsum, acc) triples
 // go to the workspace and k_combine adds them in split order.  The split count depends on (L, S, H) only, never on N.
 // No float atomics; an image's bits do not depend on the rest of the batch.
-// Range: |x| 2^act_exp <= 65504 for every q / k / v value that takes part (valid keys, unpadded queries); a launch that sees a
-// value beyond it (or a non-finite one) ORs the overflow flag, like every split-fp16 kernel of this library.
-#include "common.h"
+// Range: |x| 2^act_exp <= 65504 for every q / k / v value that takes part (valid keys, unpadded queries).
+#include "attention_f16s.h"
 #include <type_traits>
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float NEG_HUGE = -1.0e30f;
-constexpr int ROW_REF0 = -(1 << 24);     // row reference before the first tile
-constexpr float LSE_NONE = 1.0e30f;      // row statistic of a padded query row / an image without a valid key
-constexpr int P_EXP = 15;                // p is formed as 2^(x - R + 15): its fp16 lo part stays normal down to p = 2^-18 max
 
 template <int D_, int NCT_, int WAVES_>
 struct Cfg {
@@ -70,23 +59,6 @@ struct Args {
     float pre, c1, out_mul;
 };
 
-__device__ __forceinline__ void split8(const float (&x)[8], float pre, f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; e += 2) {
-        f16x2 h2, l2;
-        split2(f32x2{x[e], x[e + 1]} * f32x2{pre, pre}, h2, l2);
-        hi[e] = h2.x; hi[e + 1] = h2.y;
-        lo[e] = l2.x; lo[e + 1] = l2.y;
-    }
-}
-
-__device__ __forceinline__ bool out_of_range(const float (&x)[8], float pre) {
-    bool bad = false;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bad |= !(fabsf(x[e]) * pre <= 65504.0f);
-    return bad;
-}
-
 // One key tile on its way from global memory to LDS: fp32 in registers while the previous tile is computed.
 template <class C>
 struct Staged {
@@ -106,7 +78,7 @@ struct Staged {
             const int key = c / C::NS, sl = c % C::NS;
             const int j = j0 + key;
             const bool ok = c < C::KT * C::NS && j < a.S && (!km || km[j]);
-            float4 u = make_float4(0.f, 0.f, 0.f, 0.f), w = u;
+            float4 u = make_float4(0.f, 0.f, 0.f, 0.f), w = u;                 // (load8 into a zeroed kx[ci] costs registers in every form)
             if (ok) {
                 const float* p = kb + (size_t)j * Cst + sl * 8;
                 u = *reinterpret_cast<const float4*>(p);
@@ -118,12 +90,11 @@ struct Staged {
 #pragma unroll
         for (int ci = 0; ci < C::VCH; ++ci) {
             const int c = tid + ci * C::NT;
-            const int d = c & 31, g = c >> 5;                       // g = 4 ct + 2 u + h: the slot of MFMA (ct, u), half-wave h
-            // position e of the slot holds key 32 ct + 16 u + 4 h + (e < 4 ? e : e + 4): accumulator registers 8 u .. 8 u + 7
-            const int kbase = 32 * (g >> 2) + 16 * ((g >> 1) & 1) + 4 * (g & 1);
+            const int d = c & 31, g = c >> 5;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int j = j0 + kbase + (e < 4 ? e : e + 4);
+                // attention_f16s.h: tplane_row(j0, g, e), written out: through the call the one-wave form of D = 16 takes two more registers
+                const int j = j0 + (32 * (g >> 2) + 16 * ((g >> 1) & 1) + 4 * (g & 1)) + (e < 4 ? e : e + 4);
                 const bool ok = c < 32 * C::VS && d < C::D && j < a.S && (!km || km[j]);
                 vx[ci][e] = ok ? vb[(size_t)j * Cst + d] : 0.f;
             }
@@ -173,19 +144,12 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_full_attention(Args a) {
     constexpr int KT = C::KT, QS = D / 16, ROWS = 32 * WAVES;
     __shared__ __attribute__((aligned(16))) unsigned char lds_all[2 * C::STAGE];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-    // block -> (split, image-head z, row block Ib): the row blocks of one z share an XCD's L2 (common.h: tile_coords)
+    // block -> (split, image-head z, row block Ib)
     const int Z = a.N * a.H;
     const int per = a.nI * Z;
-    const int sp = blockIdx.x / per, id = blockIdx.x - sp * per;
+    const int sp = blockIdx.x / per;
     int z, Ib;
-    if ((Z & 7) == 0) {
-        const int xcd = id & 7, li = id >> 3;
-        z = xcd + 8 * (li / a.nI);
-        Ib = li % a.nI;
-    } else {
-        z = id / a.nI;
-        Ib = id - z * a.nI;
-    }
+    tile_coords_of(blockIdx.x - sp * per, a.nI, Z, z, Ib);
     const int n = z / a.H, hh = z - n * a.H;
     const int Cst = a.H * D;
     const int i0 = Ib * ROWS + 32 * wave;
@@ -198,12 +162,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_full_attention(Args a) {
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
         float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (qok) {
-            const float* p = a.q + ((size_t)n * a.L + irow) * Cst + hh * D + 16 * s + 8 * h;
-            const float4 u = *reinterpret_cast<const float4*>(p);
-            const float4 w = *reinterpret_cast<const float4*>(p + 4);
-            x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w; x[4] = w.x; x[5] = w.y; x[6] = w.z; x[7] = w.w;
-        }
+        if (qok) load8(a.q + ((size_t)n * a.L + irow) * Cst + hh * D + 16 * s + 8 * h, x);
         bad |= out_of_range(x, a.pre);
         split8(x, a.pre, qh[s], ql[s]);
     }
@@ -211,8 +170,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_full_attention(Args a) {
     f32x16 tacc;
 #pragma unroll
     for (int r = 0; r < 16; ++r) tacc[r] = 0.f;
-    int R = ROW_REF0;                      // integer row reference, equal in lanes l and l + 32
-    float sum = 0.f, comp = 0.f;           // this half-wave's share of the row sum (Kahan-compensated per tile)
+    RowState row;
 
     const int ntile = (a.S + KT - 1) / KT;
     const int t0 = sp * a.tps;
@@ -237,6 +195,8 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_full_attention(Args a) {
         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
+        // attention_f16s.h: score_tile, written out: through the call hipcc gives the one-wave form of D = 32 one register more, which
+        // crosses an allocation block (168 -> 176) and costs a wave per SIMD
 #pragma unroll
         for (int s = 0; s < QS; ++s) {
             f16x8 ch[NCT], cl[NCT];
@@ -261,7 +221,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_full_attention(Args a) {
         for (int ct = 0; ct < NCT; ++ct) kv[ct] = (unsigned)(km >> (32 * ct)) >> (4 * h);
         auto key_ok = [&](int ct, int r) { return ((kv[ct] >> ((r & 3) + 8 * (r >> 2))) & 1u) != 0; };
 
-        // ---- row reference: ceil of the running maximum (log2 domain), agreed between the two half-waves
+        // ---- row reference from the tile's maximum (log2 domain)
         float tm = NEG_HUGE;
         if (ragged) {
 #pragma unroll
@@ -275,20 +235,13 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_full_attention(Args a) {
                 for (int r = 0; r < 16; ++r) tm = fmaxf(tm, acc[ct][r]);
         }
         tm *= a.c1;                                                                        // c1 > 0
-        int Rn = (int)ceilf(fminf(fmaxf(tm, -1.0e6f), 1.0e6f));
-        Rn = Rn > R ? Rn : R;
-        const int Ro = __shfl_xor(Rn, 32, 64);
-        Rn = Rn > Ro ? Rn : Ro;
-        if (__any(Rn != R)) {                                                              // rare after the first tiles
-            int d = R - Rn;                                                                // <= 0
-            d = d < -200 ? -200 : d;                                                       // 2^-200 flushes every fp32 to zero already
-            sum = ldexpf(sum, d);
-            comp = ldexpf(comp, d);
+        const int Rn = row.next_ref(tm);
+        if (__any(Rn != row.R)) {                                                          // rare after the first tiles
+            const int d = row.rescale(Rn);
 #pragma unroll
             for (int r = 0; r < 16; ++r) tacc[r] = ldexpf(tacc[r], __shfl(d, mfma32_row(r, h), 64));   // register r: query mfma32_row(r, h)
-            R = Rn;
         }
-        const float nR = (float)(P_EXP - R);
+        const float nR = (float)(P_EXP_FWD - row.R);
         float t = 0.f;
         auto pv_tile = [&](auto ragged_c) {
             constexpr bool RAGGED = decltype(ragged_c)::value;
@@ -317,17 +270,13 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_full_attention(Args a) {
         };
         if (ragged) pv_tile(std::true_type{});
         else pv_tile(std::false_type{});
-        // the tile's 32 terms summed on their own, then added with Kahan compensation (emm_bilinear_f16s.hip: rowstat_update)
-        const float y = t - comp;
-        const float ns = sum + y;
-        comp = (ns - sum) - y;
-        sum = ns;
+        row.add_tile(t);
 
         if (more) bad |= st.store(lds_all + ((jt + 1 - t0) & 1) * C::STAGE, a.pre, tid, check);
         __syncthreads();
     }
-    sum -= comp;
-    const float rsum = sum + shfl_xor_f(sum, 32);          // both halves carry the same reference R
+    const float rsum = row.total();
+    const int R = row.R;
     if (a.overflow && __any(bad) && lane == 0) atomicOr(a.overflow, 1);
 
     // ---- store: the lane holds channel d = l31 of queries i0 + mfma32_row(r, h); the row's sum sits in lane (row)
@@ -346,7 +295,7 @@ __global__ __launch_bounds__(64 * WAVES, 2) void k_full_attention(Args a) {
     }
     const float den = (qok && rsum > 0.f) ? rsum : 0.f;    // 0: a padded query row / no valid key -> exact zeros
     // the row statistic the backward recomputes p from: p = 2^(x - R + 15) / rsum = 2^(x - lse2); a row without softmax gets +1e30 (p = 0)
-    if (a.lse && h == 0 && irow < a.L) a.lse[(size_t)z * a.L + irow] = den > 0.f ? (float)(R - P_EXP) + log2f(rsum) : LSE_NONE;
+    if (a.lse && h == 0 && irow < a.L) a.lse[(size_t)z * a.L + irow] = den > 0.f ? (float)(R - P_EXP_FWD) + log2f(rsum) : LSE_NONE;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int rr = mfma32_row(r, h);
@@ -375,41 +324,13 @@ __global__ __launch_bounds__(256) void k_combine(Args a, int D) {
     float num = 0.f, den = 0.f;
     for (int sp = 0; sp < a.nsplit; ++sp) {
         const size_t pr = (z * a.nsplit + sp) * a.L + i;
-        int e = a.part_ref[pr] - R;
-        e = e < -200 ? -200 : e;
+        const int e = rescale_exp(a.part_ref[pr], R);
         num += ldexpf(a.part_acc[pr * D + d], e);
         den += ldexpf(a.part_sum[pr], e);
     }
     const bool qok = !a.qm || a.qm[(size_t)n * a.L + i];
     a.out[((size_t)n * a.L + i) * (a.H * D) + hh * D + d] = (qok && den > 0.f) ? num / den * a.out_mul : 0.f;
-    if (a.lse && d == 0) a.lse[z * a.L + i] = (qok && den > 0.f) ? (float)(R - P_EXP) + log2f(den) : LSE_NONE;
-}
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// How a call is cut: S <= 32 -> one wave per (image, head, 32 queries) and a 32-key tile; else 128 queries x 64-key tiles, with
-// the key axis split when an image alone would start fewer than 64 workgroups.  A function of (L, S, H) only.
-struct Plan {
-    bool small;
-    int nI, ntile, nsplit, tps;
-};
-inline Plan plan(int L, int S, int H) {
-    Plan p;
-    p.small = S <= 32;
-    const int rows = p.small ? 32 : 128, kt = p.small ? 32 : 64;
-    p.nI = (L + rows - 1) / rows;
-    p.ntile = (S + kt - 1) / kt;
-    int ns = 1;
-    const long wg = (long)H * p.nI;
-    if (!p.small && wg < 64 && p.ntile >= 8) {
-        ns = (int)(64 / wg);
-        if (ns > p.ntile / 4) ns = p.ntile / 4;
-        if (ns > 8) ns = 8;
-        if (ns < 1) ns = 1;
-    }
-    p.tps = (p.ntile + ns - 1) / ns;
-    p.nsplit = (p.ntile + p.tps - 1) / p.tps;        // no empty split
-    return p;
+    if (a.lse && d == 0) a.lse[z * a.L + i] = (qok && den > 0.f) ? (float)(R - P_EXP_FWD) + log2f(den) : LSE_NONE;
 }
 
 int launch_forward(const float* q, const float* k, const float* v, int N, int L, int S, int H, int D, const unsigned char* q_mask,
@@ -418,7 +339,8 @@ int launch_forward(const float* q, const float* k, const float* v, int N, int L,
     if (N == 0) return FAR_OK;
     if (!q || !k || !v || !out || N < 0 || L <= 0 || S <= 0 || H <= 0 || (D != 16 && D != 32) || act_exp < -24 || act_exp > 8)
         return FAR_EINVAL;
-    const Plan p = plan(L, S, H);
+    const bool small = S <= 32;                // one wave per (image, head, 32 queries) and a 32-key tile (attention_f16s.h: split_plan)
+    const SplitPlan p = split_plan(L, S, H, small);
     const long blocks = (long)N * H * p.nI * p.nsplit;
     if (blocks > 0x7fffffffL || (long)N * H > 0x7fffffffL) return FAR_EINVAL;
     Args a;
@@ -437,7 +359,7 @@ int launch_forward(const float* q, const float* k, const float* v, int N, int L,
         a.part_ref = (int*)(b + align256(rows * D * 4) + align256(rows * 4));
     }
     const dim3 grid((unsigned)blocks);
-    if (p.small) {
+    if (small) {
         if (D == 32) hipLaunchKernelGGL((k_full_attention<32, 1, 1>), grid, dim3(64), 0, stream, a);
         else hipLaunchKernelGGL((k_full_attention<16, 1, 1>), grid, dim3(64), 0, stream, a);
     } else {
@@ -458,7 +380,7 @@ extern "C" {
 // Bytes of workspace far_full_attention_f16s needs for these sizes (0 when the key axis is not split; no GPU involved).
 size_t far_full_attention_workspace_bytes(int N, int L, int S, int H, int D) {
     if (N <= 0 || L <= 0 || S <= 0 || H <= 0 || (D != 16 && D != 32)) return 0;
-    const Plan p = plan(L, S, H);
+    const SplitPlan p = split_plan(L, S, H, S <= 32);
     if (p.nsplit <= 1) return 0;
     const size_t rows = (size_t)N * H * p.nsplit * L;
     return align256(rows * D * 4) + 2 * align256(rows * 4);

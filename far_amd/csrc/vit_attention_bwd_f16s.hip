@@ -3,8 +3,8 @@
 // Per (image n, head h), c = 1 / 8, with the training forward's saved row statistic lse2_i = log2 sum_j 2^(c log2(e) q_i.k_j):
 //   p_ij = 2^(x_ij - lse2_i)      delta_i = g_i.o_i      dv_j = sum_i p_ij g_i      dp_ij = g_i.v_j      ds_ij = p_ij (dp_ij - delta_i)
 //   dq_i = c sum_j ds_ij k_j                            dk_j = c sum_i ds_ij q_i
-// A new translation unit on K22-backward's recipe (full_attention_bwd_f16s.hip: read its header first; that file stays a head-dim-16/32
-// kernel -- one 32 x 32 output block per wave, a 32-row transposed plane).  Three launches, no (L, S)-sized tensor:
+// The backward recipe of attention_f16s.h (read its header first) in K22-backward's shape (full_attention_bwd_f16s.hip; that file stays
+// a head-dim-16/32 kernel -- one 32 x 32 output block per wave, a 32-row transposed plane).  Three launches, no (L, S)-sized tensor:
 //   k_prep   delta (Z, H, L) from g and the saved output (16 lanes x float4 per head, a fixed tree), the per-image max |g| and max |v| as
 //            integer atomicMax on the float bits -- order-independent; one per workgroup of 32 tokens --, and the range guard of q, k, v, g.
 //   k_bwd<KEYS = false>  dq: a workgroup owns 128 query rows (a lane ONE query) and walks the keys in tiles of 64.
@@ -33,15 +33,9 @@
 //            per barrier.  64 it is, as in the forward.
 // The walked axis is not split (the forward does not split either); launch geometry depends on (L, S, H) and the image index only.
 // No float atomics, no data handed between the workgroups of one launch, bit-identical from run to run.  No masks (K23 has none).
-#include "common.h"
+#include "attention_f16s.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float LSE_NONE = 1.0e30f;      // row statistic of a walked row past the end: p = 2^(x - 1e30) = 0
-constexpr int P_EXP = 14;                // p in [0, 1] enters the dv product as p 2^14
-constexpr int G_EXP = 12;                // max |g| 2^ge in [2^12, 2^13)
 
 constexpr int D = 64;
 constexpr int KT = 64, NCT = KT / 32;    // walked rows per tile, 32-row score blocks per tile
@@ -74,43 +68,6 @@ struct Args {
     int Z, L, S, H, nI, act_exp;
     float pre, c1, c;
 };
-
-__device__ __forceinline__ void split8(const float (&x)[8], float pre, f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; e += 2) {
-        f16x2 h2, l2;
-        split2(f32x2{x[e], x[e + 1]} * f32x2{pre, pre}, h2, l2);
-        hi[e] = h2.x; hi[e + 1] = h2.y;
-        lo[e] = l2.x; lo[e + 1] = l2.y;
-    }
-}
-
-__device__ __forceinline__ f16x8 round8(const float (&x)[8], float pre) {
-    f16x8 y;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) y[e] = (_Float16)(x[e] * pre);
-    return y;
-}
-
-__device__ __forceinline__ void load8(const float* p, float (&x)[8]) {
-    const float4 u = *reinterpret_cast<const float4*>(p);
-    const float4 w = *reinterpret_cast<const float4*>(p + 4);
-    x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w; x[4] = w.x; x[5] = w.y; x[6] = w.z; x[7] = w.w;
-}
-
-// The image's two exponents from the bits k_prep left: g 2^ge has its maximum in [2^12, 2^13); with |v| 2^act_exp < 2^ev,
-// |ds| <= 2 D max|g 2^ge| max|v 2^act_exp| < 2^(14 + 6 + ev), so ds 2^eds < 2^15.  A non-finite maximum (flagged by k_prep) and an
-// all-zero image get harmless exponents.
-__device__ __forceinline__ void image_exponents(const unsigned* scal, int n, int act_exp, int& ge, int& eds) {
-    const unsigned gb = scal[2 * n], vb = scal[2 * n + 1];
-    ge = G_EXP - ((int)(gb >> 23) - 127);
-    const int ev = (int)(vb >> 23) - 127 + 1 + act_exp;
-    eds = 1 - 6 - ev;
-    if (gb >= 0x7f800000u) ge = 0;
-    if (vb >= 0x7f800000u) eds = 0;
-    ge = ge < -100 ? -100 : (ge > 100 ? 100 : ge);
-    eds = eds < -60 ? -60 : (eds > 60 ? 60 : eds);
-}
 
 // ---- delta, the per-image maxima and the range guard.  A workgroup takes PREP_TOK consecutive tokens of ONE image and one side (query
 // rows: g, out, q; key rows: k, v), a wave a quarter of them; 16 lanes x float4 are one head's 64 channels, so a wave covers four heads
@@ -207,12 +164,10 @@ struct Staged {
 #pragma unroll
         for (int ci = 0; ci < VCH; ++ci) {
             const int c = tid + ci * NT;
-            const int d = c & 63, g = c >> 6;                       // g = 4 ct + 2 u + h: the slot of MFMA (ct, u), half-wave h
-            // position e of the slot holds row 32 ct + 16 u + 4 h + (e < 4 ? e : e + 4): accumulator registers 8 u .. 8 u + 7
-            const int kbase = 32 * (g >> 2) + 16 * ((g >> 1) & 1) + 4 * (g & 1);
+            const int d = c & 63, g = c >> 6;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int j = j0 + kbase + (e < 4 ? e : e + 4);
+                const int j = tplane_row(j0, g, e);
                 const bool ok = j < Wn;
                 t1[ci][e] = ok ? b1[(size_t)j * r1 + d] : 0.f;
                 if constexpr (KEYS) t2[ci][e] = ok ? b2[(size_t)j * r2 + d] : 0.f;
@@ -259,18 +214,8 @@ __global__ __launch_bounds__(NT, KEYS ? 1 : 2) void k_bwd(Args a) {
     constexpr int STAGE = Lds<KEYS>::STAGE, OFF_ST = Lds<KEYS>::OFF_ST;
     __shared__ __attribute__((aligned(16))) unsigned char lds_all[2 * STAGE];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-    // block -> (image-head z, row block Ib), as in the forward
-    const int ZH = a.Z * a.H;
-    const int id = blockIdx.x;
-    int z, Ib;
-    if ((ZH & 7) == 0) {
-        const int xcd = id & 7, li = id >> 3;
-        z = xcd + 8 * (li / a.nI);
-        Ib = li % a.nI;
-    } else {
-        z = id / a.nI;
-        Ib = id - z * a.nI;
-    }
+    int z, Ib;                             // block -> (image-head z, row block Ib), as in the forward
+    tile_coords_of(blockIdx.x, a.nI, a.Z * a.H, z, Ib);
     const int n = z / a.H, hh = z - n * a.H;
     const int Rn = KEYS ? a.S : a.L;       // owned axis
     const int Wn = KEYS ? a.L : a.S;       // walked axis
@@ -279,7 +224,7 @@ __global__ __launch_bounds__(NT, KEYS ? 1 : 2) void k_bwd(Args a) {
     const bool ook = irow < Rn;
 
     int ge, eds;
-    image_exponents(a.scal, n, a.act_exp, ge, eds);
+    image_exponents<6>(a.scal, n, a.act_exp, ge, eds);
     const float gpre = ldexpf(1.0f, ge);
     const float dsmul = ldexpf(1.0f, eds);
     const int dexp = ge + a.act_exp;                       // dp = (g 2^ge) . (v 2^act_exp): delta joins it at that scale
@@ -345,6 +290,8 @@ __global__ __launch_bounds__(NT, KEYS ? 1 : 2) void k_bwd(Args a) {
         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[ct][r] = dpa[ct][r] = 0.f;
+        // attention_f16s.h: score_tile, written out for the scores: with both products through the call the dk / dv kernel takes two
+        // more registers
 #pragma unroll
         for (int s = 0; s < QS; ++s) {
             f16x8 ch[NCT], cl[NCT];
@@ -361,22 +308,7 @@ __global__ __launch_bounds__(NT, KEYS ? 1 : 2) void k_bwd(Args a) {
 #pragma unroll
             for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[ct], xh[s], acc[ct], 0, 0, 0);
         }
-#pragma unroll
-        for (int s = 0; s < QS; ++s) {
-            f16x8 ch[NCT], cl[NCT];
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                const int off = OFF_A2 + row_off(32 * ct + l31, 2 * s + h);
-                ch[ct] = *reinterpret_cast<const f16x8*>(lds + off);
-                cl[ct] = *reinterpret_cast<const f16x8*>(lds + PLANE + off);
-            }
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) dpa[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], yh[s], dpa[ct], 0, 0, 0);
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) dpa[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], yl[s], dpa[ct], 0, 0, 0);
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) dpa[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[ct], yh[s], dpa[ct], 0, 0, 0);
-        }
+        score_tile<row_off, PLANE>(dpa, lds + OFF_A2, l31, h, yh, yl);
         // accumulator register r of tile column ct is walked row 32 ct + mfma32_row(r, h); the lane is the owned row
         const int nvalid = Wn - jt * KT;                                       // >= 1: walked rows of this tile that exist
 #pragma unroll
@@ -403,7 +335,7 @@ __global__ __launch_bounds__(NT, KEYS ? 1 : 2) void k_bwd(Args a) {
                     const bool ok = KEYS ? ook : (32 * ct + mfma32_row(r, h) < nvalid);
                     p = ok ? p : 0.f;
                     dsh[e] = (_Float16)(p * ((dpa[ct][r] - dd[e]) * dsmul));
-                    if (KEYS) ph[e] = (_Float16)(p * (float)(1 << P_EXP));
+                    if (KEYS) ph[e] = (_Float16)(p * (float)(1 << P_EXP_BWD));
                 }
 #pragma unroll
                 for (int ob = 0; ob < NOB; ++ob) {
@@ -420,7 +352,7 @@ __global__ __launch_bounds__(NT, KEYS ? 1 : 2) void k_bwd(Args a) {
 
     // ---- store: the lane holds channels l31 and 32 + l31 of owned rows i0 + mfma32_row(r, h).  ds carried 2^(ge + act_exp + eds), the
     // transposed q | k plane 2^act_exp; p 2^14 and g 2^ge
-    const int e1 = -(ge + 2 * a.act_exp + eds), e2 = -(P_EXP + ge);
+    const int e1 = -(ge + 2 * a.act_exp + eds), e2 = -(P_EXP_BWD + ge);
     float* const d1 = KEYS ? a.dk + (size_t)n * a.dkv_img + (size_t)hh * a.dkv_head : a.dq + (size_t)n * a.dq_img + (size_t)hh * a.dq_head;
     float* const d2 = KEYS ? a.dv + (size_t)n * a.dkv_img + (size_t)hh * a.dkv_head : nullptr;
     const long drow = KEYS ? a.dkv_row : a.dq_row;
@@ -439,7 +371,7 @@ __global__ __launch_bounds__(NT, KEYS ? 1 : 2) void k_bwd(Args a) {
 }
 
 // per image: 256 bytes for the two maxima, then delta (H, L) rounded up to 256 bytes -- linear in Z
-inline size_t image_bytes(int L, int H) { return 256 + (((size_t)H * L * 4 + 255) & ~(size_t)255); }
+inline size_t image_bytes(int L, int H) { return 256 + align256((size_t)H * L * 4); }
 
 }  // namespace
 

@@ -2,8 +2,8 @@
 //
 // Operator (reference: interiornetStreetlearn_8ptVit/src/modules/vision_transformer.py:250-258, inference, no dropout, no masks):
 //   out[n, l, h, :] = sum_s softmax_s(q[n,l,h,:] . k[n,s,h,:] / sqrt(64)) v[n,s,h,:]
-// A new translation unit on K22's recipe (full_attention_f16s.hip: read its header first); K22 itself stays a 32-channel kernel
-// (one 32 x 32 output block per wave, a 32-row v^T plane) and keeps refusing head dim 64.  What differs here:
+// The forward recipe of attention_f16s.h (read its header first) in K22's shape (full_attention_f16s.hip); K22 itself stays a
+// 32-channel kernel (one 32 x 32 output block per wave, a 32-row v^T plane) and keeps refusing head dim 64.  What differs here:
 //   layout   q, k, v are addressed by (image, head, row) strides, rows of 64 contiguous floats: the head planes (3h, Z, N, 64) that
 //            the qkv Linear writes with out_planes = 3h (the layout K2 reads in place) and the concatenated (Z, N, h 64) form are
 //            the same code.  out is (Z, L, h 64) with the heads concatenated: what the `proj` Linear reads.
@@ -15,22 +15,14 @@
 //   keys     no masks: a key takes part when its index is below S.  Keys past S are written as zeros and SELECTED to p = 0 (never
 //            exp'ed into the sum); the validity of a tile is arithmetic, no mask word in LDS.
 // As in K22: one workgroup = 128 query rows of one (image, head), 32 per wave; the next tile's fp32 loads are in flight while this
-// one is computed; online softmax in the log2 domain with the INTEGER row reference R = ceil(running maximum), so a rescale is an
-// exact power of two; p = 2^(x - R + 15); the tile's row-sum terms are added with Kahan compensation; out = acc / rowsum 2^-act_exp.
+// one is computed; out = acc / rowsum 2^-act_exp.
 // The (L, S) scores never reach memory, there is no workspace, no float atomics, and the launch geometry depends on (L, H) and the
 // image index only: an image's output bits do not depend on the batch.  The key axis is not split (K22 does for short L).
-// Range: |x| 2^act_exp <= 65504 for every q / k / v value that takes part; a launch that sees a value beyond it (or a non-finite
-// one) ORs the overflow flag, like every split-fp16 kernel of this library.
-#include "common.h"
+// Range: |x| 2^act_exp <= 65504 for every q / k / v value that takes part.
+#include "attention_f16s.h"
 #include <type_traits>
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-constexpr float NEG_HUGE = -1.0e30f;
-constexpr int ROW_REF0 = -(1 << 24);     // row reference before the first tile
-constexpr int P_EXP = 15;                // p is formed as 2^(x - R + 15): its fp16 lo part stays normal down to p = 2^-18 max
 
 constexpr int D = 64;                    // head dim
 constexpr int KT = 64, NCT = KT / 32;    // keys per tile, 32-key score blocks per tile
@@ -56,23 +48,6 @@ struct Args {
     float pre, c1, out_mul;
 };
 
-__device__ __forceinline__ void split8(const float (&x)[8], float pre, f16x8& hi, f16x8& lo) {
-#pragma unroll
-    for (int e = 0; e < 8; e += 2) {
-        f16x2 h2, l2;
-        split2(f32x2{x[e], x[e + 1]} * f32x2{pre, pre}, h2, l2);
-        hi[e] = h2.x; hi[e + 1] = h2.y;
-        lo[e] = l2.x; lo[e + 1] = l2.y;
-    }
-}
-
-__device__ __forceinline__ bool out_of_range(const float (&x)[8], float pre) {
-    bool bad = false;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) bad |= !(fabsf(x[e]) * pre <= 65504.0f);
-    return bad;
-}
-
 // One key tile on its way from global memory to LDS: fp32 in registers while the previous tile is computed.
 struct Staged {
     float kx[KCH][8];
@@ -85,24 +60,17 @@ struct Staged {
             const int c = tid + ci * NT;
             const int key = c >> 3, sl = c & 7;
             const int j = j0 + key;
-            float4 u = make_float4(0.f, 0.f, 0.f, 0.f), w = u;
-            if (j < a.S) {
-                const float* p = kb + (size_t)j * a.kv_row + sl * 8;
-                u = *reinterpret_cast<const float4*>(p);
-                w = *reinterpret_cast<const float4*>(p + 4);
-            }
-            kx[ci][0] = u.x; kx[ci][1] = u.y; kx[ci][2] = u.z; kx[ci][3] = u.w;
-            kx[ci][4] = w.x; kx[ci][5] = w.y; kx[ci][6] = w.z; kx[ci][7] = w.w;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) kx[ci][e] = 0.f;
+            if (j < a.S) load8(kb + (size_t)j * a.kv_row + sl * 8, kx[ci]);
         }
 #pragma unroll
         for (int ci = 0; ci < VCH; ++ci) {
             const int c = tid + ci * NT;
-            const int d = c & 63, g = c >> 6;                       // g = 4 ct + 2 u + h: the slot of MFMA (ct, u), half-wave h
-            // position e of the slot holds key 32 ct + 16 u + 4 h + (e < 4 ? e : e + 4): accumulator registers 8 u .. 8 u + 7
-            const int kbase = 32 * (g >> 2) + 16 * ((g >> 1) & 1) + 4 * (g & 1);
+            const int d = c & 63, g = c >> 6;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const int j = j0 + kbase + (e < 4 ? e : e + 4);
+                const int j = tplane_row(j0, g, e);
                 vx[ci][e] = j < a.S ? vb[(size_t)j * a.kv_row + d] : 0.f;
             }
         }
@@ -138,18 +106,8 @@ struct Staged {
 __global__ __launch_bounds__(NT, 2) void k_vit_attention(Args a) {
     __shared__ __attribute__((aligned(16))) unsigned char lds_all[2 * STAGE];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
-    // block -> (image-head z, row block Ib): the row blocks of one z share an XCD's L2 (common.h: tile_coords)
-    const int ZH = a.Z * a.H;
-    const int id = blockIdx.x;
-    int z, Ib;
-    if ((ZH & 7) == 0) {
-        const int xcd = id & 7, li = id >> 3;
-        z = xcd + 8 * (li / a.nI);
-        Ib = li % a.nI;
-    } else {
-        z = id / a.nI;
-        Ib = id - z * a.nI;
-    }
+    int z, Ib;                             // block -> (image-head z, row block Ib)
+    tile_coords_of(blockIdx.x, a.nI, a.Z * a.H, z, Ib);
     const int n = z / a.H, hh = z - n * a.H;
     const int i0 = Ib * ROWS + 32 * wave;
     const int irow = i0 + l31;
@@ -161,12 +119,7 @@ __global__ __launch_bounds__(NT, 2) void k_vit_attention(Args a) {
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
         float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (qok) {
-            const float* p = a.q + (size_t)n * a.q_img + (size_t)hh * a.q_head + (size_t)irow * a.q_row + 16 * s + 8 * h;
-            const float4 u = *reinterpret_cast<const float4*>(p);
-            const float4 w = *reinterpret_cast<const float4*>(p + 4);
-            x[0] = u.x; x[1] = u.y; x[2] = u.z; x[3] = u.w; x[4] = w.x; x[5] = w.y; x[6] = w.z; x[7] = w.w;
-        }
+        if (qok) load8(a.q + (size_t)n * a.q_img + (size_t)hh * a.q_head + (size_t)irow * a.q_row + 16 * s + 8 * h, x);
         bad |= out_of_range(x, a.pre);
         split8(x, a.pre, qh[s], ql[s]);
     }
@@ -176,8 +129,7 @@ __global__ __launch_bounds__(NT, 2) void k_vit_attention(Args a) {
     for (int ob = 0; ob < NOB; ++ob)
 #pragma unroll
         for (int r = 0; r < 16; ++r) tacc[ob][r] = 0.f;
-    int R = ROW_REF0;                      // integer row reference, equal in lanes l and l + 32
-    float sum = 0.f, comp = 0.f;           // this half-wave's share of the row sum (Kahan-compensated per tile)
+    RowState row;
 
     const float* const kb = a.k + (size_t)n * a.kv_img + (size_t)hh * a.kv_head;
     const float* const vb = a.v + (size_t)n * a.kv_img + (size_t)hh * a.kv_head;
@@ -200,28 +152,13 @@ __global__ __launch_bounds__(NT, 2) void k_vit_attention(Args a) {
         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[ct][r] = 0.f;
-#pragma unroll
-        for (int s = 0; s < QS; ++s) {
-            f16x8 ch[NCT], cl[NCT];
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
-                const int off = row_off(32 * ct + l31, 2 * s + h);
-                ch[ct] = *reinterpret_cast<const f16x8*>(lds + off);
-                cl[ct] = *reinterpret_cast<const f16x8*>(lds + PLANE + off);
-            }
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], qh[s], acc[ct], 0, 0, 0);
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch[ct], ql[s], acc[ct], 0, 0, 0);
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl[ct], qh[s], acc[ct], 0, 0, 0);
-        }
+        score_tile<row_off, PLANE>(acc, lds, l31, h, qh, ql);
         // validity of this lane's keys: accumulator register r of score block ct is key 32 ct + mfma32_row(r, h) of the tile
         const int nvalid = a.S - jt * KT;                                                  // >= 1
         const bool ragged = nvalid < KT;                                                   // workgroup-uniform: the last tile only
         auto key_ok = [&](int ct, int r) { return 32 * ct + mfma32_row(r, h) < nvalid; };
 
-        // ---- row reference: ceil of the running maximum (log2 domain), agreed between the two half-waves
+        // ---- row reference from the tile's maximum (log2 domain)
         float tm = NEG_HUGE;
         if (ragged) {
 #pragma unroll
@@ -235,24 +172,17 @@ __global__ __launch_bounds__(NT, 2) void k_vit_attention(Args a) {
                 for (int r = 0; r < 16; ++r) tm = fmaxf(tm, acc[ct][r]);
         }
         tm *= a.c1;                                                                        // c1 > 0
-        int Rn = (int)ceilf(fminf(fmaxf(tm, -1.0e6f), 1.0e6f));
-        Rn = Rn > R ? Rn : R;
-        const int Ro = __shfl_xor(Rn, 32, 64);
-        Rn = Rn > Ro ? Rn : Ro;
-        if (__any(Rn != R)) {                                                              // rare after the first tiles
-            int d = R - Rn;                                                                // <= 0
-            d = d < -200 ? -200 : d;                                                       // 2^-200 flushes every fp32 to zero already
-            sum = ldexpf(sum, d);
-            comp = ldexpf(comp, d);
+        const int Rn = row.next_ref(tm);
+        if (__any(Rn != row.R)) {                                                          // rare after the first tiles
+            const int d = row.rescale(Rn);
 #pragma unroll
             for (int r = 0; r < 16; ++r) {                                                 // register r: query mfma32_row(r, h)
                 const int dr = __shfl(d, mfma32_row(r, h), 64);
 #pragma unroll
                 for (int ob = 0; ob < NOB; ++ob) tacc[ob][r] = ldexpf(tacc[ob][r], dr);
             }
-            R = Rn;
         }
-        const float nR = (float)(P_EXP - R);
+        const float nR = (float)(P_EXP_FWD - row.R);
         float t = 0.f;
         auto pv_tile = [&](auto ragged_c) {
             constexpr bool RAGGED = decltype(ragged_c)::value;
@@ -284,23 +214,18 @@ __global__ __launch_bounds__(NT, 2) void k_vit_attention(Args a) {
         };
         if (ragged) pv_tile(std::true_type{});
         else pv_tile(std::false_type{});
-        // the tile's 32 terms summed on their own, then added with Kahan compensation (emm_bilinear_f16s.hip: rowstat_update)
-        const float y = t - comp;
-        const float ns = sum + y;
-        comp = (ns - sum) - y;
-        sum = ns;
+        row.add_tile(t);
 
         if (more) bad |= st.store(lds_all + ((jt + 1) & 1) * STAGE, a.pre, tid, check);
         __syncthreads();
     }
-    sum -= comp;
-    const float rsum = sum + shfl_xor_f(sum, 32);          // both halves carry the same reference R
+    const float rsum = row.total();
     if (a.overflow && __any(bad) && lane == 0) atomicOr(a.overflow, 1);
 
     // ---- store: the lane holds channels l31 and 32 + l31 of queries i0 + mfma32_row(r, h); the row's sum sits in lane (row)
     const float den = (qok && rsum > 0.f) ? rsum : 0.f;
     // the row statistic the backward recomputes p from: p = 2^(x - R + 15) / rsum = 2^(x - lse2), in the units of the unscaled inputs
-    if (a.lse && h == 0 && qok) a.lse[(size_t)z * a.L + irow] = den > 0.f ? (float)(R - P_EXP) + log2f(rsum) : 1.0e30f;
+    if (a.lse && h == 0 && qok) a.lse[(size_t)z * a.L + irow] = den > 0.f ? (float)(row.R - P_EXP_FWD) + log2f(rsum) : LSE_NONE;
     float* const ob0 = a.out + (size_t)n * a.L * a.H * D + (size_t)hh * D + l31;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {

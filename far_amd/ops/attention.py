@@ -26,15 +26,26 @@ def linear_attention(q, k, v, nhead, q_mask=None, kv_mask=None, eps=1e-6):
     _lib.check(rc, 'far_linear_attention_f32')
     return out
 
-def _full_attention_args(q, k, v, nhead, q_mask, kv_mask):
-    """The argument checks K22's front ends share -> (N, L, S, C, D, q_mask, kv_mask) with the masks as contiguous uint8 (or None)."""
-    for t in (q, k, v):
+def _on_gpu(*ts):
+    for t in ts:
         if not t.is_cuda:
             raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+
+def _fp32(*ts):
+    for t in ts:
+        if t.dtype != torch.float32:
+            raise _lib.FarHipError(f'expected dtype {torch.float32}, got {t.dtype}')
+
+def _qkv_shape(q, k, v, what, b):
+    """GPU tensors q (b, L, C), k, v (b, S, C) -> (b, L, S, C); `b` is the batch axis's letter in the message."""
+    _on_gpu(q, k, v)
     if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
-        raise _lib.FarHipError(f'full_attention: q (N, L, C), k, v (N, S, C); got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}')
-    N, L, C = q.shape
-    S = k.shape[1]
+        raise _lib.FarHipError(f'{what}: q ({b}, L, C), k, v ({b}, S, C); got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}')
+    return q.shape[0], q.shape[1], k.shape[1], q.shape[2]
+
+def _full_attention_args(q, k, v, nhead, q_mask, kv_mask):
+    """The argument checks K22's front ends share -> (N, L, S, C, D, q_mask, kv_mask) with the masks as contiguous uint8 (or None)."""
+    N, L, S, C = _qkv_shape(q, k, v, 'full_attention', 'N')
     if nhead < 1 or C % nhead:
         raise _lib.FarHipError(f'full_attention: {C} channels do not divide into {nhead} heads')
     D = C // nhead
@@ -126,11 +137,8 @@ def full_attention_train(q, k, v, nhead, q_mask=None, kv_mask=None):
 def _vit_attention_launch(q, k, v, Z, L, S, nhead, q_strides, kv_strides):
     """far_vit_attention_f16s on operands whose layout the caller has established (strides in floats: image, head, row)."""
     lib = _lib.load()
-    for t in (q, k, v):
-        if not t.is_cuda:
-            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
-        if t.dtype != torch.float32:
-            raise _lib.FarHipError(f'expected dtype {torch.float32}, got {t.dtype}')
+    _on_gpu(q, k, v)
+    _fp32(q, k, v)
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
         raise NotImplementedError('vit_attention (K23, far_vit_attention_f16s) is the inference front end: run it under torch.no_grad() '
                                   'or on tensors that need no gradient; ops.vit_attention_train / vit_attention_train_qkv are the '
@@ -153,16 +161,7 @@ def vit_attention(q, k, v, nhead):
     exist).  Operands are split around the thread's activation exponent; a value beyond its range ORs ops.overflow_flag.  Inputs
     that need gradients raise NotImplementedError (vit_attention_train is the form with gradients).  vit_attention_planes is the
     same kernel on the head planes the qkv Linear writes."""
-    for t in (q, k, v):
-        if not t.is_cuda:
-            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
-    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
-        raise _lib.FarHipError(f'vit_attention: q (Z, L, C), k, v (Z, S, C); got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}')
-    Z, L, C = q.shape
-    S = k.shape[1]
-    if nhead < 1 or C != nhead * 64:
-        raise _lib.FarHipError(f'vit_attention: head dim 64 only (K23), got {C} channels in {nhead} heads '
-                               '(head dims 16 and 32: ops.full_attention)')
+    Z, L, S, C = _vit_views(q, k, v, nhead, 'vit_attention', other='ops.full_attention')
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
     return _vit_attention_launch(q, k, v, Z, L, S, nhead, (L * C, 64, C), (S * C, 64, C))
 
@@ -170,8 +169,7 @@ def vit_attention_planes(planes, nhead):
     """K23 on the head planes ops.linear_f16s(x, qkv, out_planes=3 * nhead) writes: planes (3 nhead, Z, N, 64) fp32 contiguous --
     plane h is q of head h, nhead + h is k, 2 nhead + h is v (the layout K2 reads in place; no copy here either).  Returns
     (Z, N, nhead * 64) with the heads concatenated: what the `proj` Linear reads.  Checks and refusals as vit_attention."""
-    if not planes.is_cuda:
-        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    _on_gpu(planes)
     if planes.dim() != 4 or planes.shape[0] != 3 * nhead or planes.shape[3] != 64 or not planes.is_contiguous():
         raise _lib.FarHipError(f'vit_attention_planes: planes (3 * nhead, Z, N, 64) contiguous, head dim 64 only (K23); got '
                                f'{tuple(planes.shape)} for {nhead} heads')
@@ -179,22 +177,14 @@ def vit_attention_planes(planes, nhead):
     st = (N * 64, Z * N * 64, 64)
     return _vit_attention_launch(planes[:nhead], planes[nhead:2 * nhead], planes[2 * nhead:], Z, N, N, nhead, st, st)
 
-def _vit_views(q, k, v, nhead, what):
-    """The checks of vit_attention on (Z, L | S, nhead * 64) fp32 GPU tensors whose rows are contiguous (views into a wider
-    projection included) -> (Z, L, S, C, q strides, kv strides), strides in floats as (image, head, row)."""
-    for t in (q, k, v):
-        if not t.is_cuda:
-            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
-    if q.dim() != 3 or k.dim() != 3 or k.shape != v.shape or q.shape[0] != k.shape[0] or q.shape[2] != k.shape[2]:
-        raise _lib.FarHipError(f'{what}: q (Z, L, C), k, v (Z, S, C); got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}')
-    Z, L, C = q.shape
-    S = k.shape[1]
+def _vit_views(q, k, v, nhead, what, other='ops.full_attention_train'):
+    """The checks K23's front ends share on (Z, L | S, nhead * 64) fp32 GPU tensors -> (Z, L, S, C); `other`: the op the message
+    names for head dims 16 and 32."""
+    Z, L, S, C = _qkv_shape(q, k, v, what, 'Z')
     if nhead < 1 or C != nhead * 64:
         raise _lib.FarHipError(f'{what}: head dim 64 only (K23), got {C} channels in {nhead} heads '
-                               '(head dims 16 and 32: ops.full_attention_train)')
-    for t in (q, k, v):
-        if t.dtype != torch.float32:
-            raise _lib.FarHipError(f'expected dtype {torch.float32}, got {t.dtype}')
+                               f'(head dims 16 and 32: {other})')
+    _fp32(q, k, v)
     return Z, L, S, C
 
 def _row_strides(t):
@@ -231,8 +221,7 @@ def vit_attention_bwd(q, k, v, out, lse, g, nhead, act_exp=None, into=None):
     into, returned as views of it.  Z = 0, L = 0 or S = 0: zeros."""
     lib = _lib.load()
     Z, L, S, C = _vit_views(q, k, v, nhead, 'vit_attention_bwd')
-    if not g.is_cuda:
-        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    _on_gpu(g)
     g = g.float().contiguous()
     if tuple(g.shape) != (Z, L, C) or tuple(out.shape) != (Z, L, C) or tuple(lse.shape) != (Z, nhead, L):
         raise _lib.FarHipError(f'vit_attention_bwd: out, g (Z, L, C) and lse (Z, nhead, L); got {tuple(out.shape)}, {tuple(g.shape)}, '
@@ -302,13 +291,11 @@ def vit_attention_train_qkv(qkv, nhead):
     reference's reshape(B, N, 3, H, 64), vision_transformer.py:252): q, k, v are read in place, and the backward returns ONE
     (Z, N, 3 C) gradient that the kernels wrote in place -- no chunk, no cat, no copies.  Returns (Z, N, C), heads concatenated:
     the bits of vit_attention_train on the three column slices."""
-    if not qkv.is_cuda:
-        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    _on_gpu(qkv)
     if qkv.dim() != 3 or nhead < 1 or qkv.shape[2] != 3 * nhead * 64:
         raise _lib.FarHipError(f'vit_attention_train_qkv: qkv (Z, N, 3 * nhead * 64), head dim 64 only (K23); got {tuple(qkv.shape)} '
                                f'for {nhead} heads')
-    if qkv.dtype != torch.float32:
-        raise _lib.FarHipError(f'expected dtype {torch.float32}, got {qkv.dtype}')
+    _fp32(qkv)
     return _VitAttentionFn.apply(nhead, True, qkv)
 
 class _LinearAttentionFn(torch.autograd.Function):

@@ -34,6 +34,30 @@ def test_backward_workspace_query_needs_no_gpu():
     assert ws(2, 100, 500, 8, 24) == 0 and ws(0, 100, 500, 8, 32) == 0
 
 
+# (N, L, S, H, D) -> bytes of the forward's and the backward's workspace: every branch of the split plan (key axis split for the
+# forward and dq, query axis split for dk / dv, the ns <= ntile / 4 and ns <= 8 limits, fewer than 8 tiles, the one-wave form of
+# the forward alone and of both, 64 workgroups or more per image without a split)
+K22_WORKSPACE = {
+    (2, 300, 1200, 8, 32): (1305600, 1248256),
+    (2, 1200, 300, 8, 32): (0, 2534656),
+    (1, 127, 4799, 3, 32): (414720, 391936),
+    (1, 40, 4800, 1, 16): (23040, 20992),
+    (3, 25, 25, 8, 16): (0, 2816),
+    (2, 33, 32, 8, 32): (0, 2560),
+    (64, 4800, 4800, 8, 32): (0, 9830912),
+}
+K23_BWD_WORKSPACE = {(2, 576, 576, 3, 64): 14336, (3, 130, 65, 3, 64): 6144}
+
+
+def test_workspace_sizes_are_pinned():
+    lib = _lib.load()
+    for shape, (fwd, bwd) in K22_WORKSPACE.items():
+        assert lib.far_full_attention_workspace_bytes(*shape) == fwd, shape
+        assert lib.far_full_attention_bwd_workspace_bytes(*shape) == bwd, shape
+    for shape, n in K23_BWD_WORKSPACE.items():
+        assert lib.far_vit_attention_bwd_workspace_bytes(*shape) == n, shape
+
+
 def test_switch_defaults_and_setter():
     from far_amd.loftr import LoFTR
     from far_amd.loftr.transformer import FullAttention, LoFTREncoderLayer

@@ -31,6 +31,8 @@ CASES = {
     't4': dict(seed=2204, N=2, L=500, S=100, D=32, amp=1.5),       # short key side for the dq kernel
     't5a': dict(seed=2205, N=6, L=25, S=25, D=16, amp=1.2),        # the <= 32-key one-wave form
     't5b': dict(seed=2206, N=6, L=25, S=25, D=16, amp=2.94),
+    't5c': dict(seed=2209, N=2, L=40, S=25, D=16, amp=1.2),        # S <= 32 < L: the forward one-wave, the backward tiled
+    't5d': dict(seed=2210, N=2, L=25, S=40, D=16, amp=1.2),        # the mirror: only the short side differs
     't6': dict(seed=2207, N=2, L=200, S=150, D=16, amp=1.5),       # D = 16 on the tiled form
     't7': dict(seed=2208, N=2, L=180, S=150, D=32, amp=1.5, q_valid=(130, 180), kv_valid=(150, 70)),
     't7e': dict(seed=2208, N=2, L=180, S=150, D=32, amp=1.5, q_valid=(130, 180), kv_valid=(150, 0)),   # image 1 without a valid key

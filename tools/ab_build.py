@@ -1,5 +1,6 @@
 """Same-box A/B aid: builds far_amd/lib/libfar_hip_base.so from the sources of a git revision (default HEAD) next to the
-working tree's library, so that a timing script can load either (FAR_HIP_LIB=far_amd/lib/libfar_hip_base.so).  python tools/ab_build.py [rev]"""
+working tree's library, with the flags build.py gives each file, so that a timing script or tools/ab_outputs.py can load either
+(FAR_HIP_LIB=far_amd/lib/libfar_hip_base.so).  python tools/ab_build.py [rev]"""
 import os
 import subprocess
 import sys
@@ -23,7 +24,7 @@ for n in sorted(os.listdir(tmp)):
                 all(open(os.path.join(B.CSRC, h)).read() == open(os.path.join(tmp, h)).read() for h in os.listdir(tmp) if h.endswith(('.h', '.inc'))):
             o = os.path.join(B.LIBDIR, n[:-4] + '.o')            # unchanged: reuse the working tree's object
         else:
-            subprocess.check_call([B.HIPCC] + B.FLAGS + ['-I', tmp, '-c', os.path.join(tmp, n), '-o', o])
+            subprocess.check_call([B.HIPCC] + B.FLAGS + B.per_file_flags(n) + ['-I', tmp, '-c', os.path.join(tmp, n), '-o', o])
         objs.append(o)
 # a base of another ABI would be called with this tree's argument lists (far_amd/_lib.py checks it at load: refuse here already)
 import re  # noqa: E402
