@@ -286,7 +286,7 @@ def partial_write_check(path):
 
 
 # headers whose device code issues LDS-DMA: a file that includes one is scanned like a file that issues it itself
-LDS_DMA_HEADERS = ('k1_f16s.h',)
+LDS_DMA_HEADERS = ('k1_f16s.h', 'k1_train_f16s.h')
 
 
 def uses_lds_dma(src):

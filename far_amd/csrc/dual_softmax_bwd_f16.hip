@@ -16,57 +16,12 @@
 //             maps swapped (dF0: rows = L side; dF1: rows = S side).  The sparse part 2 W is M scaled row additions.
 //   Arithmetic: plain fp16 operands, fp32 accumulation, for both contractions (gradients: ~1e-3 relative, measured in
 //   tests/test_train_kernels_gpu.py against float64 autograd); u, v are scaled by a power of two so that G <= 1 in fp16.
-#include "dual_softmax_common.h"
+#include "k1_train_f16s.h"
 #include <algorithm>
 
-namespace far_k1b {
+namespace {
 
-using namespace far_ds;
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
-constexpr int C = 256;
-constexpr int NS = C / 16;
-constexpr int KT = 32;                   // columns per tile
-constexpr int ROWB = C * 2;              // bytes per fp16 row of the row-major planes
-constexpr int TILE_X = KT * ROWB;        // 16 KiB: tile of the row-major (swizzled) hi plane, for the score recompute
-constexpr int TROW = 80;                 // bytes per channel row of a transposed tile: 32 positions x 2 B + 16 B pad
-constexpr int TILE_T = C * TROW;         // 20 KiB
-constexpr int STAGE = TILE_X + TILE_T;   // 36 KiB
-constexpr float PRESCALE = 16.0f;
-constexpr float HUGE_F = 1.0e30f;
-
-// position of column c (0..31) inside a transposed tile row: MFMA step u = c >> 4 takes, from lane half h, the eight
-// accumulator registers r = 8 u + e, which hold the columns 16 u + 4 h + (e & 3) + 8 (e >> 2)
-__device__ __host__ inline int tpos(int c) {
-    const int u = c >> 4, c16 = c & 15, h = (c16 >> 2) & 1, e = (c16 & 3) + 4 * (c16 >> 3);
-    return (2 * u + h) * 8 + e;
-}
-
-// x [Z][N][256] fp32 -> transposed fp16 tiles [Z][Np / 32][256 ch][TROW], value * 2^4, rows >= N zero
-__global__ void k1b_prep_t(const float* __restrict__ x, int Z, int N, int Np, unsigned char* __restrict__ out) {
-    const long total = (long)Z * (Np / KT) * C * 4;                       // one thread = 8 positions of one channel row
-    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        const int q = (int)(t & 3);                                       // which 8 positions
-        const int ch = (int)((t >> 2) & (C - 1));
-        const long zt = t >> 10;                                          // z * ntile + tile
-        const int ntile = Np / KT;
-        const int jt = (int)(zt % ntile);
-        const long z = zt / ntile;
-        f16x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            // inverse of tpos for position p = 8 q + e:  u = q >> 1, h = q & 1, column = 16 u + 4 h + (e & 3) + 8 (e >> 2)
-            const int c = 16 * (q >> 1) + 4 * (q & 1) + (e & 3) + 8 * (e >> 2);
-            const int i = jt * KT + c;
-            v[e] = i < N ? (_Float16)(x[((size_t)z * N + i) * C + ch] * PRESCALE) : (_Float16)0.f;
-        }
-        *reinterpret_cast<f16x8*>(out + (size_t)zt * TILE_T + ch * TROW + q * 16) = v;
-    }
-}
+constexpr int STAGE = PLANE32 + TILE_T;   // 36 KiB: the hi plane tile + the transposed tile
 
 // p_k = conf at (b_k, i_k, j_k): one wave per position, float64 dot product of the fp32 features
 __global__ __launch_bounds__(256) void k1b_pos_conf(const float* __restrict__ f0, const float* __restrict__ f1, int L, int S, int Sp,
@@ -113,10 +68,7 @@ __global__ void k1b_scatter_uv(const int64_t* __restrict__ pb, const int64_t* __
 __global__ void k1b_side(const float* __restrict__ u, const float2* __restrict__ stat, const float* __restrict__ dmax,
                          const float* __restrict__ dinv, int Z, int N, int Np, const unsigned* __restrict__ wmax_bits,
                          float* __restrict__ wsc, float* __restrict__ lnorm) {
-    const float wmax = __uint_as_float(*wmax_bits);
-    int e = 0;
-    if (wmax > 0.f) { (void)frexpf(wmax, &e); e = -(e + 3); }
-    const float sc = ldexpf(1.0f, e);
+    const float sc = ldexpf(1.0f, grad_scale_exp(wmax_bits, 3));
     const long total = (long)Z * Np;
     for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
         const int i = (int)(t % Np);
@@ -132,14 +84,9 @@ __global__ void k1b_side(const float* __restrict__ u, const float2* __restrict__
     }
 }
 
-__device__ __forceinline__ void dma_lin(unsigned char* lds, const unsigned char* g, int bytes, int tid, int wave) {
-    for (int o = 0; o < bytes; o += 4096)
-        __builtin_amdgcn_global_load_lds((gptr_t)(g + o + tid * 16), (lptr_t)(lds + o + wave * 1024), 16, 0, 0);
-}
-
 // out[z][row][256] = coef * sum_cols G[row][col] * B[col][:],   G = alpha_row 2^(x - rho_row) + beta_col 2^(x - gamma_col)
 //   ah   row-side hi plane  [Z][Nrp][256] fp16 (swizzled LDS image of k1_prep)
-//   bh   column-side hi plane, same layout; bt: column-side transposed tiles (k1b_prep_t)
+//   bh   column-side hi plane, same layout; bt: column-side transposed tiles (k1_prep_t)
 // grid: Z * Nrp / 128 workgroups of 4 waves; wave = 32 rows x 256 channels of the output (128 accumulator registers)
 __global__ __launch_bounds__(256, 2) void k1_bwd(const _Float16* __restrict__ ah, const _Float16* __restrict__ bh,
                                                  const unsigned char* __restrict__ bt, int Z, int Nr, int Nc, int Nrp, int Ncp,
@@ -165,14 +112,14 @@ __global__ __launch_bounds__(256, 2) void k1_bwd(const _Float16* __restrict__ ah
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
     float* const cw = reinterpret_cast<float*>(lds + 2 * STAGE);  // [2 stages][beta 32 | gamma 32]
-    const int ntile = Ncp / KT;
+    const int ntile = Ncp / GT;
     auto request = [&](int jt, int st) {
         unsigned char* base = lds + st * STAGE;
-        dma_lin(base, reinterpret_cast<const unsigned char*>(bh + ((size_t)z * Ncp + (size_t)jt * KT) * C), TILE_X, tid, wave);
-        dma_lin(base + TILE_X, bt + ((size_t)z * ntile + jt) * TILE_T, TILE_T, tid, wave);
-        if (tid < KT) {
-            cw[st * 64 + tid] = beta[(size_t)z * Ncp + jt * KT + tid];
-            cw[st * 64 + 32 + tid] = gamma[(size_t)z * Ncp + jt * KT + tid];
+        dma_lin(base, reinterpret_cast<const unsigned char*>(bh + ((size_t)z * Ncp + (size_t)jt * GT) * C), PLANE32, tid, wave);
+        dma_lin(base + PLANE32, bt + ((size_t)z * ntile + jt) * TILE_T, TILE_T, tid, wave);
+        if (tid < GT) {
+            cw[st * 64 + tid] = beta[(size_t)z * Ncp + jt * GT + tid];
+            cw[st * 64 + 32 + tid] = gamma[(size_t)z * Ncp + jt * GT + tid];
         }
     };
     request(0, 0);
@@ -207,7 +154,7 @@ __global__ __launch_bounds__(256, 2) void k1_bwd(const _Float16* __restrict__ ah
             }
         }
         // ---- out[row][channel] += G[row][col] * B[col][channel]: A = G (registers), B = transposed tile (LDS)
-        const unsigned char* ts = xs + TILE_X;
+        const unsigned char* ts = xs + PLANE32;
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -217,10 +164,7 @@ __global__ __launch_bounds__(256, 2) void k1_bwd(const _Float16* __restrict__ ah
             }
     }
     // ---- epilogue: undo the scalings (operands x 2^4, weights x 2^e) and apply -kappa
-    const float wmax = __uint_as_float(*wmax_bits);
-    int e = 0;
-    if (wmax > 0.f) { (void)frexpf(wmax, &e); e = -(e + 3); }
-    const float coef = -kappa * ldexpf(1.0f, -e) / PRESCALE;
+    const float coef = -kappa * ldexpf(1.0f, -grad_scale_exp(wmax_bits, 3)) / PRESCALE;
     const int row0 = Ib * 128 + 32 * wave;
 #pragma unroll
     for (int nt = 0; nt < 8; ++nt)
@@ -258,33 +202,25 @@ struct WsB {
 };
 inline WsB carve_b(unsigned char* p, size_t o, int Z, int L, int S) {
     WsB w;
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
-    auto take = [&](size_t n) { unsigned char* r = p ? p + o : nullptr; o += align256(n); return r; };
-    w.at = take((size_t)Z * (Lp / KT) * TILE_T);
-    w.bt = take((size_t)Z * (Sp / KT) * TILE_T);
-    w.u = (float*)take((size_t)Z * L * 4); w.v = (float*)take((size_t)Z * S * 4);
-    w.alpha = (float*)take((size_t)Z * Lp * 4); w.rho = (float*)take((size_t)Z * Lp * 4);
-    w.beta = (float*)take((size_t)Z * Sp * 4); w.gamma = (float*)take((size_t)Z * Sp * 4);
-    w.wmax = (unsigned*)take(256);
-    w.bytes = o;
+    const int Lp = pad128(L), Sp = pad128(S);
+    Carver c{p, o};
+    w.at = c.take((size_t)Z * (Lp / GT) * TILE_T);
+    w.bt = c.take((size_t)Z * (Sp / GT) * TILE_T);
+    w.u = c.take<float>((size_t)Z * L * 4); w.v = c.take<float>((size_t)Z * S * 4);
+    w.alpha = c.take<float>((size_t)Z * Lp * 4); w.rho = c.take<float>((size_t)Z * Lp * 4);
+    w.beta = c.take<float>((size_t)Z * Sp * 4); w.gamma = c.take<float>((size_t)Z * Sp * 4);
+    w.wmax = c.take<unsigned>(256);
+    w.bytes = c.o;
     return w;
 }
 
-}  // namespace far_k1b
-
-// ---- glue with dual_softmax_f16s.hip (same translation-unit-independent layout of the forward workspace) ----
-size_t far_k1_fwd_ws_bytes(int Z, int L, int S);
-int far_k1_stats_launch(const float* f0, const float* f1, int Z, int L, int S, float temperature, void* ws, int* overflow,
-                        hipStream_t stream);
-void far_k1_fwd_views(void* ws, int Z, int L, int S, const _Float16** ah, const _Float16** bh, const float2** rowstat,
-                      const float** cmax, const float** cinv, float* c1);
+}  // namespace
 
 extern "C" {
 
 size_t far_coarse_train_workspace_bytes(int Z, int L, int S, int Cc) {
-    if (Z <= 0 || L <= 0 || S <= 0 || Cc != far_k1b::C) return 0;
-    const size_t fwd = far_k1_fwd_ws_bytes(Z, L, S);
-    return far_k1b::carve_b(nullptr, fwd, Z, L, S).bytes;
+    if (Z <= 0 || L <= 0 || S <= 0 || Cc != C) return 0;
+    return carve_b(nullptr, far_k1_fwd_ws_bytes(Z, L, S), Z, L, S).bytes;
 }
 
 // Forward of the sparse coarse supervision: p_out[k] = conf_matrix[pb[k], pi[k], pj[k]] (coarse_matching.py:108-118 at the
@@ -292,7 +228,6 @@ size_t far_coarse_train_workspace_bytes(int Z, int L, int S, int Cc) {
 int far_coarse_pos_conf_f16s(const float* f0, const float* f1, int Z, int L, int S, int Cc, float temperature,
                              const int64_t* pb, const int64_t* pi, const int64_t* pj, int M, float* p_out, void* ws,
                              int* overflow, hipStream_t stream) {
-    using namespace far_k1b;
     far_clear_errors();
     if (!f0 || !f1 || !ws || Z <= 0 || L <= 0 || S <= 0 || Cc != C || M < 0 || (M > 0 && (!pb || !pi || !pj || !p_out)))
         return FAR_EINVAL;
@@ -304,7 +239,7 @@ int far_coarse_pos_conf_f16s(const float* f0, const float* f1, int Z, int L, int
         const float *cmax, *cinv;
         float c1;
         far_k1_fwd_views(ws, Z, L, S, &ah, &bh, &rowstat, &cmax, &cinv, &c1);
-        const int Sp = (S + 127) / 128 * 128;
+        const int Sp = pad128(S);
         const double k2 = 1.4426950408889634 / ((double)C * (double)temperature);
         hipLaunchKernelGGL(k1b_pos_conf, dim3(std::min((M + 3) / 4, 2048)), dim3(256), 0, stream, f0, f1, L, S, Sp, k2, pb, pi, pj, M,
                            rowstat, cmax, cinv, p_out);
@@ -317,19 +252,17 @@ int far_coarse_pos_conf_f16s(const float* f0, const float* f1, int Z, int L, int
 int far_coarse_pos_conf_bwd_f16(const float* f0, const float* f1, int Z, int L, int S, int Cc, float temperature,
                                 const int64_t* pb, const int64_t* pi, const int64_t* pj, int M, const float* w, float* df0,
                                 float* df1, void* ws, hipStream_t stream) {
-    using namespace far_k1b;
     far_clear_errors();
     if (!f0 || !f1 || !ws || !df0 || !df1 || Z <= 0 || L <= 0 || S <= 0 || Cc != C || M < 0 || (M > 0 && (!pb || !pi || !pj || !w)))
         return FAR_EINVAL;
     const WsB b = carve_b((unsigned char*)ws, far_k1_fwd_ws_bytes(Z, L, S), Z, L, S);
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const int Lp = pad128(L), Sp = pad128(S);
     const _Float16 *ah, *bh;
     const float2* rowstat;
     const float *cmax, *cinv;
     float c1;
     far_k1_fwd_views(ws, Z, L, S, &ah, &bh, &rowstat, &cmax, &cinv, &c1);
     c1 = (float)(1.4426950408889634 / ((double)C * (double)temperature * PRESCALE * PRESCALE));   // log2-domain score per unit dot
-    auto gridp = [](long n) { long g = (n + 255) / 256; return (unsigned)(g < 16384 ? (g > 0 ? g : 1) : 16384); };
     hipMemsetAsync(b.u, 0, (size_t)Z * L * 4, stream);
     hipMemsetAsync(b.v, 0, (size_t)Z * S * 4, stream);
     hipMemsetAsync(b.wmax, 0, 4, stream);
@@ -338,8 +271,8 @@ int far_coarse_pos_conf_bwd_f16(const float* f0, const float* f1, int Z, int L, 
                        (const float*)nullptr, Z, L, Lp, b.wmax, b.alpha, b.rho);
     hipLaunchKernelGGL(k1b_side, dim3(gridp((long)Z * Sp)), dim3(256), 0, stream, b.v, (const float2*)nullptr, cmax, cinv, Z, S, Sp,
                        b.wmax, b.beta, b.gamma);
-    hipLaunchKernelGGL(k1b_prep_t, dim3(gridp((long)Z * (Lp / KT) * C * 4)), dim3(256), 0, stream, f0, Z, L, Lp, b.at);
-    hipLaunchKernelGGL(k1b_prep_t, dim3(gridp((long)Z * (Sp / KT) * C * 4)), dim3(256), 0, stream, f1, Z, S, Sp, b.bt);
+    hipLaunchKernelGGL(k1_prep_t, dim3(gridp((long)Z * (Lp / GT) * C * 4)), dim3(256), 0, stream, f0, Z, L, Lp, (const uint8_t*)nullptr, b.at);
+    hipLaunchKernelGGL(k1_prep_t, dim3(gridp((long)Z * (Sp / GT) * C * 4)), dim3(256), 0, stream, f1, Z, S, Sp, (const uint8_t*)nullptr, b.bt);
     const size_t smem = 2 * STAGE + 2 * 64 * sizeof(float);
     FAR_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)k1_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     const float kappa = (float)(1.0 / ((double)C * (double)temperature));

@@ -14,7 +14,7 @@
 //                               float64 partial of the loss.  The second launch swaps the maps' roles: v_b = sum_a W_ab.
 //               k1d_pos         p_k at the positives, bit for bit as the tile pass formed it; the correction of the loss and of W
 //               k1d_finish      u, v += the positives' corrections (each row scans the M labels in order), device max of |W|, |u|, |v|
-//               k1d_loss        partials + corrections summed in a fixed order
+//               k1_focal_loss   partials + corrections summed in a fixed order
 //             No float atomics anywhere: the same bits at every launch.
 //   backward  far_coarse_dense_focal_bwd_f16  dLoss/dx = 2 W - u R - v C (log p = 2 x - lse_row - lse_col);  dF0 = kappa G F1,
 //             dF1 = kappa G^T F0.  k1d_pass<1|2> recomputes the score tile exactly as the forward did, forms G in the accumulator
@@ -22,32 +22,15 @@
 //             fp16 tile, as k1_bwd does (dual_softmax_bwd_f16.hip); launched twice with the roles swapped.  G is scaled by a
 //             power of two read from device memory (the forward's max) and carried as ONE fp16 (<1>) or as a hi + lo pair (<2>).
 //             The positives' correction 2 kappa dW_k F[other] is added by k1d_pos_rows: one wave per output row, labels in order.
-#include "k1_f16s.h"
+#include "k1_train_f16s.h"
 #include <algorithm>
-
-// ---- glue with dual_softmax_f16s.hip: the forward workspace, its masked statistics passes, its operand planes ----
-size_t far_k1_fwd_ws_bytes(int Z, int L, int S);
-int far_k1_stats_launch_masked(const float* f0, const float* f1, int Z, int L, int S, float temperature, const uint8_t* mask0,
-                               const uint8_t* mask1, void* ws, int* overflow, hipStream_t stream);
-void far_k1_fwd_planes(void* ws, int Z, int L, int S, const _Float16** ah, const _Float16** al, const _Float16** bh,
-                       const _Float16** bl, const float2** rowstat, const float2** colstat);
 
 namespace {
 
-constexpr int DT = 32;                     // columns per tile
-constexpr int PLANE32 = DT * ROWB;         // 16 KiB: one plane of a tile (row-major, swizzled: the LDS image of k1_prep)
-constexpr int TROW = 80;                   // bytes per channel row of a transposed tile: 32 positions x 2 B + 16 B pad
-constexpr int TILE_T = C * TROW;           // 20 KiB
-constexpr float P_LO = 1e-6f;
-constexpr float P_HI = (float)(1.0 - 1e-6);
 constexpr float VALID_BELOW = 1.0e29f;     // a statistic below this marks a real, unmasked position (+HUGE_F otherwise)
 
-struct FocalK {
-    float alpha, gamma, cneg;              // cneg = neg_weight / (N L S - #positives)
-    double c_lo, c_hi;                     // the negative term of an entry clamped from below / from above
-};
-
-// the negative-form focal term of an entry inside the clamp's range, and W = (d term / d p) p
+// the negative-form focal term of an entry inside the clamp's range, and W = (d term / d p) p.  (neg_w of sinkhorn_train_f16s.hip is
+// other arithmetic -- a hardware log plus a series, from the exponent of p -- and is kept apart on purpose.)
 __device__ __forceinline__ float neg_w(float p, float alpha, float gamma, float& term) {
     const float l1 = log1pf(-p);
     const float qg = __builtin_amdgcn_exp2f(gamma * __builtin_amdgcn_logf(p));
@@ -73,38 +56,8 @@ __global__ void k1d_side(const float2* __restrict__ stat, const uint8_t* __restr
     }
 }
 
-// x [Z][N][256] fp32 -> transposed fp16 tiles [Z][Np / 32][256 ch][TROW], value * 2^4, rows >= N zero; the columns of a tile in the
-// order in which the accumulator registers hold G (as k1b_prep_t of dual_softmax_bwd_f16.hip)
-__global__ void k1d_prep_t(const float* __restrict__ x, int Z, int N, int Np, unsigned char* __restrict__ out) {
-    const long total = (long)Z * (Np / DT) * C * 4;                       // one thread = 8 positions of one channel row
-    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        const int q = (int)(t & 3);
-        const int ch = (int)((t >> 2) & (C - 1));
-        const long zt = t >> 10;                                          // z * ntile + tile
-        const int ntile = Np / DT;
-        const int jt = (int)(zt % ntile);
-        const long z = zt / ntile;
-        f16x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            // position 8 q + e of the row holds column 16 u + 4 h + (e & 3) + 8 (e >> 2), u = q >> 1, h = q & 1
-            const int c = 16 * (q >> 1) + 4 * (q & 1) + (e & 3) + 8 * (e >> 2);
-            const int i = jt * DT + c;
-            v[e] = i < N ? (_Float16)(x[((size_t)z * N + i) * C + ch] * PRESCALE) : (_Float16)0.f;
-        }
-        *reinterpret_cast<f16x8*>(out + (size_t)zt * TILE_T + ch * TROW + q * 16) = v;
-    }
-}
-
-__device__ __forceinline__ void dma_lin(unsigned char* lds, const unsigned char* g, int bytes, int tid, int wave) {
-    for (int o = 0; o < bytes; o += 4096)
-        __builtin_amdgcn_global_load_lds((gptr_t)(g + o + tid * 16), (lptr_t)(lds + o + wave * 1024), 16, 0, 0);
-}
-
 __device__ __forceinline__ float scale_of(const unsigned* gmax_bits, int& e) {
-    const float gmax = __uint_as_float(*gmax_bits);
-    e = 0;
-    if (gmax > 0.f) { (void)frexpf(gmax, &e); e = -(e + 2); }             // 4 gmax 2^e <= 1
+    e = grad_scale_exp(gmax_bits, 2);                                     // 4 gmax 2^e <= 1
     e = e < -100 ? -100 : (e > 100 ? 100 : e);
     return ldexpf(1.0f, e);
 }
@@ -112,7 +65,7 @@ __device__ __forceinline__ float scale_of(const unsigned* gmax_bits, int& e) {
 // MODE 0 (loss pass): roww[z][row] = sum_cols W (written), lossp[workgroup] = the workgroup's share of sum_entries term (unless null),
 //                     gmax_bits = atomic max of |W| (unless null)
 // MODE 1 / 2 (gradient pass): out[z][row][256] = kappa g sum_cols G[row][col] B[col][:],  G = 2 W - roww_row R - colw_col C
-//   ah, al   row-side planes [Z][Nrp][256] fp16 (k1_prep); bh, bl: column-side planes; bt: column-side transposed tiles (k1d_prep_t)
+//   ah, al   row-side planes [Z][Nrp][256] fp16 (k1_prep); bh, bl: column-side planes; bt: column-side transposed tiles (k1_prep_t)
 //   rmax, rinv [Z][Nrp] / cmax, cinv [Z][Ncp]: k1d_side
 // grid: Z * Nrp / 128 workgroups of 4 waves; wave = 32 rows (x 256 channels of the output: 128 accumulator registers)
 template <int MODE>
@@ -151,14 +104,14 @@ __global__ __launch_bounds__(256, 1) void k1d_pass(const _Float16* __restrict__ 
     double lsum = 0.0;
     int nlo = 0, nhi = 0;
     float* const cw = reinterpret_cast<float*>(lds + 2 * STAGE);  // [2 stages][cmax 32 | cinv 32 | colw 32]
-    const int ntile = (Nc + DT - 1) / DT;
+    const int ntile = (Nc + GT - 1) / GT;
     auto request = [&](int jt, int st) {
         unsigned char* base = lds + st * STAGE;
-        const size_t row0 = (size_t)z * Ncp + (size_t)jt * DT;
+        const size_t row0 = (size_t)z * Ncp + (size_t)jt * GT;
         dma_lin(base, reinterpret_cast<const unsigned char*>(bh + row0 * C), PLANE32, tid, wave);
         dma_lin(base + PLANE32, reinterpret_cast<const unsigned char*>(bl + row0 * C), PLANE32, tid, wave);
-        if (MODE) dma_lin(base + 2 * PLANE32, bt + ((size_t)z * (Ncp / DT) + jt) * TILE_T, TILE_T, tid, wave);
-        if (tid < DT) {
+        if (MODE) dma_lin(base + 2 * PLANE32, bt + ((size_t)z * (Ncp / GT) + jt) * TILE_T, TILE_T, tid, wave);
+        if (tid < GT) {
             cw[st * 96 + tid] = cmax[row0 + tid];
             cw[st * 96 + 32 + tid] = cinv[row0 + tid];
             if (MODE) cw[st * 96 + 64 + tid] = colw[row0 + tid] * gs;
@@ -185,12 +138,7 @@ __global__ __launch_bounds__(256, 1) void k1d_pass(const _Float16* __restrict__ 
             const int off = l31 * ROWB + (((2 * s + h) ^ (l31 & 15)) * 16);
             const f16x8 ch = *reinterpret_cast<const f16x8*>(xs + off);
             const f16x8 cl = *reinterpret_cast<const f16x8*>(xs + PLANE32 + off);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.hi[s], sc, 0, 0, 0);
-            sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.hi[s], sx, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sc, 0, 0, 0);
-            sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sx, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sc, 0, 0, 0);
-            sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sx, 0, 0, 0);
+            score_step_both(sc, sx, ch, cl, rf.hi[s], rf.lo[s]);
         }
         // ---- this lane's row and its 16 columns  c = (r & 3) + 8 (r >> 2) + 4 h
         f16x8 gh[2], gl[2];
@@ -298,12 +246,7 @@ __global__ __launch_bounds__(256) void k1d_pos(const _Float16* __restrict__ ah, 
             const int so = 8 * ((2 * s + h) ^ (int)(j & 15)), ro = 8 * ((2 * s + h) ^ (int)(i & 15));
             const f16x8 ch = *reinterpret_cast<const f16x8*>(ca + so), cl = *reinterpret_cast<const f16x8*>(cb + so);
             const f16x8 rh = *reinterpret_cast<const f16x8*>(ra + ro), rlo = *reinterpret_cast<const f16x8*>(rl + ro);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rh, sc, 0, 0, 0);
-            sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rh, sx, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rlo, sc, 0, 0, 0);
-            sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rh, sx, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rh, sc, 0, 0, 0);
-            sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rlo, sx, 0, 0, 0);
+            score_step_both(sc, sx, ch, cl, rh, rlo);
         }
         // the diagonal: this lane's column l31 against tile row mfma32_row(r, h) == l31
         const int rd = (l31 & 3) + 4 * (l31 >> 3);
@@ -364,22 +307,6 @@ __global__ void k1d_finish(const int64_t* __restrict__ pb, const int64_t* __rest
     if ((threadIdx.x & 63) == 0 && mx > 0.f) atomicMax(gmax_bits, __float_as_uint(mx));
 }
 
-// loss = cneg * sum of the workgroups' partials + sum of the positives' corrections: one workgroup, a fixed order
-__global__ __launch_bounds__(256) void k1d_loss(const double* __restrict__ lossp, int nparts, const double* __restrict__ dl, int M,
-                                                double cneg, float* __restrict__ loss_out) {
-    __shared__ double sh[256];
-    double a = 0.0, b = 0.0;
-    for (int t = threadIdx.x; t < nparts; t += 256) a += lossp[t];
-    for (int t = threadIdx.x; t < M; t += 256) b += dl[t];
-    sh[threadIdx.x] = cneg * a + b;
-    __syncthreads();
-    for (int m = 128; m >= 1; m >>= 1) {
-        if ((int)threadIdx.x < m) sh[threadIdx.x] += sh[threadIdx.x + m];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss_out[0] = (float)sh[0];
-}
-
 // the positives' part of the gradient: df0[z, i] += 2 kappa g sum_{k: (b_k, i_k) = (z, i)} dw_k F1[z, j_k] and df1[z, j] likewise;
 // one wave per output row scans the labels in order (no atomics)
 __global__ __launch_bounds__(256) void k1d_pos_rows(const float* __restrict__ f0, const float* __restrict__ f1, int Z, int L, int S,
@@ -437,44 +364,29 @@ struct WsD {
 };
 inline WsD carve_d(unsigned char* p, size_t o, int Z, int L, int S, int M) {
     WsD w;
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const int Lp = pad128(L), Sp = pad128(S);
     const size_t Mc = M > 0 ? M : 1;
-    auto take = [&](size_t n) { unsigned char* r = p ? p + o : nullptr; o += align256(n); return r; };
-    w.at = take((size_t)Z * (Lp / DT) * TILE_T);
-    w.bt = take((size_t)Z * (Sp / DT) * TILE_T);
-    w.rmax = (float*)take((size_t)Z * Lp * 4); w.rinv = (float*)take((size_t)Z * Lp * 4); w.u = (float*)take((size_t)Z * Lp * 4);
-    w.cmax = (float*)take((size_t)Z * Sp * 4); w.cinv = (float*)take((size_t)Z * Sp * 4); w.v = (float*)take((size_t)Z * Sp * 4);
-    w.lossp = (double*)take((size_t)Z * (Lp / 128) * 8);
-    w.dl = (double*)take(Mc * 8);
-    w.dw = (float*)take(Mc * 4);
-    w.gmax = (unsigned*)take(256);
-    w.bytes = o;
+    Carver c{p, o};
+    w.at = c.take((size_t)Z * (Lp / GT) * TILE_T);
+    w.bt = c.take((size_t)Z * (Sp / GT) * TILE_T);
+    w.rmax = c.take<float>((size_t)Z * Lp * 4); w.rinv = c.take<float>((size_t)Z * Lp * 4); w.u = c.take<float>((size_t)Z * Lp * 4);
+    w.cmax = c.take<float>((size_t)Z * Sp * 4); w.cinv = c.take<float>((size_t)Z * Sp * 4); w.v = c.take<float>((size_t)Z * Sp * 4);
+    w.lossp = c.take<double>((size_t)Z * (Lp / 128) * 8);
+    w.dl = c.take<double>(Mc * 8);
+    w.dw = c.take<float>(Mc * 4);
+    w.gmax = c.take<unsigned>(256);
+    w.bytes = c.o;
     return w;
 }
 
-struct Plan {
-    FocalK fk;
-    double cpos;
+struct Plan : FocalPlan {
     int Meff, dummy;
 };
-// the normalisers and the label set of a call (loftr_loss.py:63-70: without ground truth the positive term has weight 0, and in
-// the weighted case entry (0, 0, 0) leaves the negative term as well)
-inline Plan make_plan(int Z, int L, int S, int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, bool masks) {
-    Plan pl;
-    const long npos = no_gt ? 0 : M;
-    const double nneg = (double)Z * (double)L * (double)S - (double)npos;
-    pl.fk.alpha = alpha;
-    pl.fk.gamma = gamma;
-    pl.fk.cneg = nneg > 0 ? (float)((double)neg_weight / nneg) : 0.f;
-    pl.fk.c_lo = -(double)alpha * pow(1e-6, (double)gamma) * log1p(-1e-6);
-    pl.fk.c_hi = -(double)alpha * pow(1.0 - 1e-6, (double)gamma) * log(1e-6);
-    pl.cpos = npos > 0 ? (double)pos_weight / (double)npos : 0.0;
-    pl.dummy = no_gt && masks;
-    pl.Meff = no_gt ? (masks ? 1 : 0) : M;
-    return pl;
+// make_plan with the label set of a call: without ground truth, a weighted batch has the single label (0, 0, 0), which leaves the
+// negative term as well (loftr_loss.py:63-70)
+inline Plan make_plan_ds(int Z, int L, int S, int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, bool masks) {
+    return Plan{make_plan(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt), no_gt ? (masks ? 1 : 0) : M, no_gt && masks};
 }
-
-inline unsigned gridp(long n) { long g = (n + 255) / 256; return (unsigned)(g < 16384 ? (g > 0 ? g : 1) : 16384); }
 
 constexpr size_t SMEM_F = 2 * (2 * PLANE32) + 2 * 96 * sizeof(float);
 constexpr size_t SMEM_B = 2 * (2 * PLANE32 + TILE_T) + 2 * 96 * sizeof(float);
@@ -498,11 +410,11 @@ int far_coarse_dense_focal_f16s(const float* f0, const float* f1, int Z, int L, 
                                 void* ws, int* overflow, hipStream_t stream) {
     far_clear_errors();
     if (!f0 || !f1 || !ws || !loss_out || bad_shape(Z, L, S, Cc, M) || (M > 0 && (!pb || !pi || !pj)) || !(temperature > 0.f)) return FAR_EINVAL;
-    const Plan pl = make_plan(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt, mask0 || mask1);
+    const Plan pl = make_plan_ds(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt, mask0 || mask1);
     int rc = far_k1_stats_launch_masked(f0, f1, Z, L, S, temperature, mask0, mask1, ws, overflow, stream);
     if (rc != FAR_OK) return rc;
     const WsD d = carve_d((unsigned char*)ws, far_k1_fwd_ws_bytes(Z, L, S), Z, L, S, M);
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const int Lp = pad128(L), Sp = pad128(S);
     const _Float16 *ah, *al, *bh, *bl;
     const float2 *rowstat, *colstat;
     far_k1_fwd_planes(ws, Z, L, S, &ah, &al, &bh, &bl, &rowstat, &colstat);
@@ -524,7 +436,7 @@ int far_coarse_dense_focal_f16s(const float* f0, const float* f1, int Z, int L, 
                        (const float*)nullptr, pl.fk, (unsigned*)nullptr, (double*)nullptr, (const float*)nullptr, 0.f, (float*)nullptr);
     hipLaunchKernelGGL(k1d_finish, dim3(gridp((long)Z * (L + S))), dim3(256), 0, stream, pb, pi, pj, pl.Meff, pl.dummy, (const float*)d.dw, Z,
                        L, S, Lp, Sp, d.u, d.v, d.gmax);
-    hipLaunchKernelGGL(k1d_loss, dim3(1), dim3(256), 0, stream, (const double*)d.lossp, nparts, (const double*)d.dl, pl.Meff,
+    hipLaunchKernelGGL(k1_focal_loss, dim3(1), dim3(256), 0, stream, (const double*)d.lossp, nparts, (const double*)d.dl, pl.Meff,
                        (double)pl.fk.cneg, loss_out);
     return far_check_launch();
 }
@@ -536,16 +448,16 @@ int far_coarse_dense_focal_bwd_f16(const float* f0, const float* f1, int Z, int 
     far_clear_errors();
     if (!f0 || !f1 || !ws || !gup || !df0 || !df1 || bad_shape(Z, L, S, Cc, M) || (M > 0 && (!pb || !pi || !pj)) || !(temperature > 0.f))
         return FAR_EINVAL;
-    const Plan pl = make_plan(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt, mask0 || mask1);
+    const Plan pl = make_plan_ds(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt, mask0 || mask1);
     const WsD d = carve_d((unsigned char*)ws, far_k1_fwd_ws_bytes(Z, L, S), Z, L, S, M);
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const int Lp = pad128(L), Sp = pad128(S);
     const _Float16 *ah, *al, *bh, *bl;
     const float2 *rowstat, *colstat;
     far_k1_fwd_planes(ws, Z, L, S, &ah, &al, &bh, &bl, &rowstat, &colstat);
     const float c1 = (float)(1.4426950408889634 / ((double)C * (double)temperature * PRESCALE * PRESCALE));
     const float kappa = (float)(1.0 / ((double)C * (double)temperature));
-    hipLaunchKernelGGL(k1d_prep_t, dim3(gridp((long)Z * (Lp / DT) * C * 4)), dim3(256), 0, stream, f0, Z, L, Lp, d.at);
-    hipLaunchKernelGGL(k1d_prep_t, dim3(gridp((long)Z * (Sp / DT) * C * 4)), dim3(256), 0, stream, f1, Z, S, Sp, d.bt);
+    hipLaunchKernelGGL(k1_prep_t, dim3(gridp((long)Z * (Lp / GT) * C * 4)), dim3(256), 0, stream, f0, Z, L, Lp, (const uint8_t*)nullptr, d.at);
+    hipLaunchKernelGGL(k1_prep_t, dim3(gridp((long)Z * (Sp / GT) * C * 4)), dim3(256), 0, stream, f1, Z, S, Sp, (const uint8_t*)nullptr, d.bt);
     FAR_ONCE_PER_DEVICE(
         hipFuncSetAttribute((const void*)k1d_pass<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM_B);
         hipFuncSetAttribute((const void*)k1d_pass<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SMEM_B));

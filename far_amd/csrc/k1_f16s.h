@@ -5,6 +5,9 @@
 //   dma_tile     one 64-row tile of both planes into LDS
 //   score_tile   three v_mfma_f32_32x32x16_f16 per 16 channels (hi.hi + hi.lo + lo.hi, fp32 accumulate)
 // Each including file gets its own copy in its anonymous namespace (one translation unit per .hip file).
+// The training files include k1_train_f16s.h, which adds the 32-column gradient tile, its prep kernel and the dense focal loss's
+// shared pieces on top of this header.  The library-internal functions through which they reach the two matchers (far_k1_*,
+// far_skh_history_launch) are declared at the end of this file, which their defining files include as well.
 #pragma once
 #include "dual_softmax_common.h"
 
@@ -130,6 +133,21 @@ __device__ __forceinline__ void score_tile(f32x16 (&acc)[2], const unsigned char
 }
 
 }  // namespace
+
+// ---- library-internal glue between the matchers and the training files (not part of the C ABI) ----
+// dual_softmax_f16s.hip -> dual_softmax_bwd_f16.hip, dual_softmax_dense_f16s.hip: the forward workspace (the training workspaces begin
+// behind it), its statistics passes (operand planes + row statistics + dense column statistics, as far_coarse_match_f16s prepares them;
+// masked: with optional padded masks (Z, L) / (Z, S)), and views of what they left: the hi planes with the column (max, 1 / sum) of the
+// sparse form (c1 is set by the caller), or all four planes with the (max, sum) statistics of both axes
+size_t far_k1_fwd_ws_bytes(int Z, int L, int S);
+int far_k1_stats_launch(const float* f0, const float* f1, int Z, int L, int S, float temperature, void* ws, int* overflow,
+                        hipStream_t stream);
+int far_k1_stats_launch_masked(const float* f0, const float* f1, int Z, int L, int S, float temperature, const uint8_t* mask0,
+                               const uint8_t* mask1, void* ws, int* overflow, hipStream_t stream);
+void far_k1_fwd_views(void* ws, int Z, int L, int S, const _Float16** ah, const _Float16** bh, const float2** rowstat,
+                      const float** cmax, const float** cinv, float* c1);
+void far_k1_fwd_planes(void* ws, int Z, int L, int S, const _Float16** ah, const _Float16** al, const _Float16** bh,
+                       const _Float16** bl, const float2** rowstat, const float2** colstat);
 
 // sinkhorn_f16s.hip -> sinkhorn_train_f16s.hip (library-internal, not part of the C ABI): the matcher's operand preparation and its T
 // iterations (the same k_skh_stats launches: the bits of inference) with every (u^t, v^t) kept.  uh [(T+1)][Z][Lp], vh [(T+1)][Z][Sp],

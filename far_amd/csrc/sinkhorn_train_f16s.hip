@@ -23,9 +23,8 @@
 // its kernels (k_skd_*) and entry points are at the end of this file, its backward is skt_backward with k_skt_bwd<.., DENSE>.
 // Potentials, adjoint vectors and the 2T-term contraction are fp32; the weights are scaled by a power of two so that the dense part
 // sits in the fp16 range at any gradient scale (scale_exp).  No data is handed between the workgroups of one launch.
-#include "k1_f16s.h"
+#include "k1_train_f16s.h"
 #include <algorithm>
-#include <cmath>
 
 namespace {
 
@@ -33,24 +32,14 @@ constexpr float LOG2E = 1.44269504088896341f;
 constexpr int MAX_ITERS = 48;            // the column terms of a tile are staged in LDS: 2 T x 256 B per stage
 constexpr int KFOLD = 4;                 // positions per row whose weight joins the dense tile in fp32 (k_skt_bwd)
 constexpr float FOLD_MAX = 8192.0f;      // ... unless its scaled weight is above 2^13: KFOLD slots on ONE entry (duplicate positions) stay <= 2^15
-constexpr int KB = 32;                   // columns per tile of the gradient kernel
-constexpr int TILE_X = KB * ROWB;        // 16 KiB: row-major (swizzled) hi plane tile, for the score recompute
-constexpr int TROW = 80;                 // bytes per channel row of a transposed tile: 32 positions x 2 B + 16 B pad
-constexpr int TILE_T = C * TROW;         // 20 KiB
-constexpr int STAGE = 2 * TILE_X + TILE_T;   // 52 KiB: hi and lo plane tiles + the transposed tile (+ the column terms)
+constexpr int STAGE = 2 * PLANE32 + TILE_T;  // 52 KiB: hi and lo plane tiles + the transposed tile (+ the column terms)
 
 __device__ __forceinline__ float ex2(float x) { return __builtin_amdgcn_exp2f(x); }
 
 // ---- dense supervision (far_sinkhorn_dense_focal_*: the kernels are at the end of this file) ----
 constexpr float LN2 = 0.693147180559945309f;
-constexpr float P_LO = 1e-6f;                        // the loss reads q = clamp(p, 1e-6, 1 - 1e-6)
-constexpr float P_HI = (float)(1.0 - 1e-6);
 constexpr float DEAD = -0.5f * HUGE_F;               // a potential below this marks a padded or masked row / column
 
-struct FocalK {
-    float alpha, gamma, cneg;                        // cneg = neg_weight / (N L S - #positives)
-    double c_lo, c_hi;                               // the negative term of an entry clamped from below / from above
-};
 struct DenseK {                                      // what k_skt_bwd<.., DENSE> needs beyond the sparse kernel's arguments
     const float *dr, *dc;                            // k_skd_side's potentials of the row side [Z][Nrp] and the column side [Z][Ncp]
     const float* gup;                                // the upstream gradient, one device float
@@ -60,7 +49,8 @@ struct DenseK {                                      // what k_skt_bwd<.., DENSE
 // The negative-form focal term -alpha p^gamma log(1 - p) of an entry p = 2^xe inside the clamp's range, and W = (d term / d p) p.
 // p^gamma comes from the exponent; log(1 - p) is one hardware log, except below 2^-8 where 1 - p would lose p's digits (series to
 // p^4: relative error < p^4 / 5 < 5e-11).  ONE definition for the loss pass, the labels' correction and the gradient kernel: the
-// same p gives the same bits everywhere.
+// same p gives the same bits everywhere.  (neg_w of dual_softmax_dense_f16s.hip is other arithmetic -- log1pf of p itself -- and is
+// kept apart on purpose.)
 __device__ __forceinline__ float neg_w(float p, float xe, float alpha, float gamma, float& term) {
     const float om = 1.0f - p;
     const float ser = -p * (1.0f + p * (0.5f + p * (0.333333343f + p * 0.25f)));
@@ -147,6 +137,8 @@ __global__ __launch_bounds__(256) void k_skt_seed(const float* __restrict__ wb0,
 // < 2^14; plus at most KFOLD slots of <= FOLD_MAX = 2^13 each, all on that entry when positions repeat: <= 2^15) stays below
 // 3 x 2^14 = 49152 < 65504, while contributions 2^-27 of the largest are still normal fp16 numbers -- the many small softmax
 // weights of a row without a partner must not fall into the subnormals (measured: 0.6 % error with the largest weight at 2^-4).
+// Written out, not grad_scale_exp(wmax_bits, log2 P - 14) of k1_train_f16s.h: through the helper k_skt_bwd<0, 1|2> take one more
+// VGPR and AGPR and k_skt_bwd<6> one more spilled SGPR.
 __device__ __forceinline__ int scale_exp(const unsigned* wmax_bits, int nterm) {
     const float wmax = __uint_as_float(*wmax_bits);
     int e = 0;
@@ -407,38 +399,9 @@ __global__ void k_skt_pack(const float* __restrict__ uh, const float* __restrict
     }
 }
 
-// x [Z][N][256] fp32 -> transposed fp16 tiles [Z][Np / 32][256 ch][TROW] of K1's backward (columns in the order in which the
-// accumulator registers hold G), value * 2^4; rows >= N and MASKED rows zero (a masked row may hold anything, also non-finite values)
-__global__ void k_skt_prep_t(const float* __restrict__ x, int Z, int N, int Np, const uint8_t* __restrict__ mask,
-                             unsigned char* __restrict__ out) {
-    const long total = (long)Z * (Np / KB) * C * 4;                       // one thread = 8 positions of one channel row
-    for (long t = (long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long)gridDim.x * blockDim.x) {
-        const int q = (int)(t & 3);
-        const int ch = (int)((t >> 2) & (C - 1));
-        const long zt = t >> 10;                                          // z * ntile + tile
-        const int ntile = Np / KB;
-        const int jt = (int)(zt % ntile);
-        const long z = zt / ntile;
-        f16x8 v;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int c = 16 * (q >> 1) + 4 * (q & 1) + (e & 3) + 8 * (e >> 2);
-            const int i = jt * KB + c;
-            const bool ok = i < N && !(mask && !mask[(size_t)z * N + i]);
-            v[e] = ok ? (_Float16)(x[((size_t)z * N + i) * C + ch] * PRESCALE) : (_Float16)0.f;
-        }
-        *reinterpret_cast<f16x8*>(out + (size_t)zt * TILE_T + ch * TROW + q * 16) = v;
-    }
-}
-
-__device__ __forceinline__ void dma_lin(unsigned char* lds, const unsigned char* g, int bytes, int tid, int wave) {
-    for (int o = 0; o < bytes; o += 4096)
-        __builtin_amdgcn_global_load_lds((gptr_t)(g + o + tid * 16), (lptr_t)(lds + o + wave * 1024), 16, 0, 0);
-}
-
 // out[z][row][256] = coef * sum_cols G[row][col] * B[col][:],   G = slots + sum_k rw^k_row cw^k_col 2^(x + re^k_row + ce^k_col)
 //   ah / al   row-side hi / lo planes [Z][Nrp][256] fp16 (swizzled LDS image of k1_prep); bh / bl: column side, same layout; bt:
-//   column-side transposed tiles (k_skt_prep_t); rw / re [nterm][Z][Nrp], cw / ce [nterm][Z][Ncp]: k_skt_pack's terms;
+//   column-side transposed tiles (k1_prep_t); rw / re [nterm][Z][Nrp], cw / ce [nterm][Z][Ncp]: k_skt_pack's terms;
 //   slot_j / slot_w [Z][Nrp][KFOLD]: the row's first positions (column, w 2^e; column -1: empty), k_skt_group<1>.
 // The scores are the split-fp16 ones of the forward (hi.hi + hi.lo + lo.hi): where a confident match makes the dense part cancel
 // the position's own weight, a relative score error delta would stay as delta |w| next to a result of (1 - P) |w|.  The sum of
@@ -500,20 +463,20 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
     const int stage = STAGE + nterm * 256 + (DENSE ? 256 : 0);    // tile planes + [nterm][W 32 | E 32] column terms (+ the dense term's potentials)
-    const int ntile = Ncp / KB;
+    const int ntile = Ncp / GT;
     auto request = [&](int jt, int st) {
         unsigned char* base = lds + st * stage;
-        dma_lin(base, reinterpret_cast<const unsigned char*>(bh + ((size_t)z * Ncp + (size_t)jt * KB) * C), TILE_X, tid, wave);
-        dma_lin(base + TILE_X, reinterpret_cast<const unsigned char*>(bl + ((size_t)z * Ncp + (size_t)jt * KB) * C), TILE_X, tid, wave);
-        dma_lin(base + 2 * TILE_X, bt + ((size_t)z * ntile + jt) * TILE_T, TILE_T, tid, wave);
+        dma_lin(base, reinterpret_cast<const unsigned char*>(bh + ((size_t)z * Ncp + (size_t)jt * GT) * C), PLANE32, tid, wave);
+        dma_lin(base + PLANE32, reinterpret_cast<const unsigned char*>(bl + ((size_t)z * Ncp + (size_t)jt * GT) * C), PLANE32, tid, wave);
+        dma_lin(base + 2 * PLANE32, bt + ((size_t)z * ntile + jt) * TILE_T, TILE_T, tid, wave);
         for (int o = tid; o < nterm * 64; o += 256) {             // whole waves: nterm * 64 is a multiple of 64
             const int k = o >> 6, c = o & 31;
-            const float* src = ((o & 32) ? ce : cw) + (size_t)k * cstride + (size_t)z * Ncp + jt * KB + c;
+            const float* src = ((o & 32) ? ce : cw) + (size_t)k * cstride + (size_t)z * Ncp + jt * GT + c;
             __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(base + STAGE + (o - lane) * 4), 4, 0, 0);
         }
         if constexpr (DENSE != 0) {
             if (wave == 0)                                        // 32 column potentials (the upper half-wave repeats them into the pad)
-                __builtin_amdgcn_global_load_lds((gptr_t)(dk.dc + (size_t)z * Ncp + jt * KB + l31), (lptr_t)(base + STAGE + nterm * 256), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(dk.dc + (size_t)z * Ncp + jt * GT + l31), (lptr_t)(base + STAGE + nterm * 256), 4, 0, 0);
         }
     };
     request(0, 0);
@@ -532,15 +495,9 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
         for (int s = 0; s < NS; ++s) {
             const int off = l31 * ROWB + (((2 * s + h) ^ (l31 & 15)) * 16);
             const f16x8 ch = *reinterpret_cast<const f16x8*>(xs + off);
-            const f16x8 cl = *reinterpret_cast<const f16x8*>(xs + TILE_X + off);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.hi[s], sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sc, 0, 0, 0);
-            if constexpr (DENSE != 0) {                           // the same entry with the two cross terms the other way round
-                sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.hi[s], sx, 0, 0, 0);
-                sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sx, 0, 0, 0);
-                sx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sx, 0, 0, 0);
-            }
+            const f16x8 cl = *reinterpret_cast<const f16x8*>(xs + PLANE32 + off);
+            score_step(sc, ch, cl, rf.hi[s], rf.lo[s]);
+            if constexpr (DENSE != 0) score_step_x(sx, ch, cl, rf.hi[s], rf.lo[s]);      // the same entry with the two cross terms the other way round
         }
         // ---- G for this lane's row and its 16 columns  c = (r & 3) + 8 (r >> 2) + 4 h; a score that is not finite can only come from a
         // masked row or column (W = 0, E = -huge there): taken as 0 so that it stays out of the products
@@ -620,7 +577,7 @@ __global__ __launch_bounds__(256, 1) void k_skt_bwd(const _Float16* __restrict__
             }
         }
         // ---- out[row][channel] += G[row][col] * B[col][channel]: A = G (registers), B = transposed tile (LDS)
-        const unsigned char* ts = xs + 2 * TILE_X;
+        const unsigned char* ts = xs + 2 * PLANE32;
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -700,15 +657,12 @@ __global__ void k_skt_dbin_sum(const float* __restrict__ part, int Z, float* __r
 //                      sum normalised p), so an entry has the same bits in both launches, in k_skd_pos and in the gradient kernel:
 //                      it is inside or outside the clamp everywhere alike.
 //     k_skd_pos        the labels: p_k with the bits of the tile pass, the correction of the loss (float64) and of W
-//     k_skd_loss       partials and corrections summed in a fixed order -> one device float
+//     k1_focal_loss    partials and corrections summed in a fixed order -> one device float
 //   backward  far_sinkhorn_dense_focal_bwd_f16  k_skd_seed (ubar^T = gup ubar, vbar^T = gup vbar, dustbin seeds 0, the labels'
 //             weights gup dW_k), then skt_backward: the sparse backward's launches with k_skt_bwd<.., DENSE> and the labels as its
 //             positions.  gup is one device float: no host read.
 // No float atomics (one integer atomicMax on float bits per wave, k_skd_pass): the same bits at every launch.
 // =====================================================================================================================
-constexpr int DT = 32;                     // columns per tile of the loss pass
-constexpr int PLANE32 = DT * ROWB;         // 16 KiB: one plane of a tile
-
 __global__ void k_skd_side(const float* __restrict__ uT, const float* __restrict__ vT, const uint8_t* __restrict__ mask0,
                            const uint8_t* __restrict__ mask1, int Z, int L, int S, int Lp, int Sp, float nrm, float* __restrict__ dr,
                            float* __restrict__ dc) {
@@ -758,13 +712,13 @@ __global__ __launch_bounds__(256, 2) void k_skd_pass(const _Float16* __restrict_
     double lsum = 0.0;
     int nlo = 0, nhi = 0;
     float* const cw = reinterpret_cast<float*>(lds + 2 * STG);    // [2 stages][32 column potentials]
-    const int ntile = (Nc + DT - 1) / DT;
+    const int ntile = (Nc + GT - 1) / GT;
     auto request = [&](int jt, int st) {
         unsigned char* base = lds + st * STG;
-        const size_t row0 = (size_t)z * Ncp + (size_t)jt * DT;
+        const size_t row0 = (size_t)z * Ncp + (size_t)jt * GT;
         dma_lin(base, reinterpret_cast<const unsigned char*>(bh + row0 * C), PLANE32, tid, wave);
         dma_lin(base + PLANE32, reinterpret_cast<const unsigned char*>(bl + row0 * C), PLANE32, tid, wave);
-        if (tid < DT) cw[st * DT + tid] = cpot[row0 + tid];
+        if (tid < GT) cw[st * GT + tid] = cpot[row0 + tid];
     };
     request(0, 0);
     for (int jt = 0; jt < ntile; ++jt) {
@@ -781,19 +735,13 @@ __global__ __launch_bounds__(256, 2) void k_skd_pass(const _Float16* __restrict_
             const int off = l31 * ROWB + (((2 * s + h) ^ (l31 & 15)) * 16);
             const f16x8 ch = *reinterpret_cast<const f16x8*>(xs + off);
             const f16x8 cl = *reinterpret_cast<const f16x8*>(xs + PLANE32 + off);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.hi[s], sc, 0, 0, 0);
-            if (SWAP) {
-                sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sc, 0, 0, 0);
-            } else {
-                sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rf.lo[s], sc, 0, 0, 0);
-                sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rf.hi[s], sc, 0, 0, 0);
-            }
+            if (SWAP) score_step_x(sc, ch, cl, rf.hi[s], rf.lo[s]);
+            else score_step(sc, ch, cl, rf.hi[s], rf.lo[s]);
         }
         // ---- this lane's row and its 16 columns  c = (r & 3) + 8 (r >> 2) + 4 h
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            const float4 c4 = *reinterpret_cast<const float4*>(cw + st * DT + 8 * q + 4 * h);
+            const float4 c4 = *reinterpret_cast<const float4*>(cw + st * GT + 8 * q + 4 * h);
             const float cc[4] = {c4.x, c4.y, c4.z, c4.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -857,9 +805,7 @@ __global__ __launch_bounds__(256) void k_skd_pos(const _Float16* __restrict__ ah
             const int so = 8 * ((2 * s + h) ^ (int)(j & 15)), ro = 8 * ((2 * s + h) ^ (int)(i & 15));
             const f16x8 ch = *reinterpret_cast<const f16x8*>(ca + so), cl = *reinterpret_cast<const f16x8*>(cb + so);
             const f16x8 rh = *reinterpret_cast<const f16x8*>(ra + ro), rlo = *reinterpret_cast<const f16x8*>(rl + ro);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rh, sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(cl, rh, sc, 0, 0, 0);
-            sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ch, rlo, sc, 0, 0, 0);
+            score_step_x(sc, ch, cl, rh, rlo);
         }
         // the diagonal: this lane's column l31 against tile row mfma32_row(r, h) == l31
         const int rd = (l31 & 3) + 4 * (l31 >> 3);
@@ -896,22 +842,6 @@ __global__ __launch_bounds__(256) void k_skd_pos(const _Float16* __restrict__ ah
             if (aw > 0.f && aw < HUGE_F) atomicMax(gmax_bits + z, __float_as_uint(aw));
         }
     }
-}
-
-// loss = cneg * sum of the workgroups' partials + sum of the labels' corrections: one workgroup, a fixed order
-__global__ __launch_bounds__(256) void k_skd_loss(const double* __restrict__ lossp, int nparts, const double* __restrict__ dl, int M,
-                                                  double cneg, float* __restrict__ loss_out) {
-    __shared__ double sh[256];
-    double a = 0.0, b = 0.0;
-    for (int t = threadIdx.x; t < nparts; t += 256) a += lossp[t];
-    for (int t = threadIdx.x; t < M; t += 256) b += dl[t];
-    sh[threadIdx.x] = cneg * a + b;
-    __syncthreads();
-    for (int m = 128; m >= 1; m >>= 1) {
-        if ((int)threadIdx.x < m) sh[threadIdx.x] += sh[threadIdx.x + m];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss_out[0] = (float)sh[0];
 }
 
 // The seeds of the adjoint recursion at t = T: ubar = gup ubar_dense, vbar = gup vbar_dense (the labels' part is added by
@@ -974,25 +904,23 @@ struct WsT {
 };
 inline WsT carve_t(void* ws, int Z, int L, int S, int T) {
     WsT w;
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
-    unsigned char* p = (unsigned char*)ws;
-    size_t o = 0;
-    auto take = [&](size_t n) { unsigned char* r = p ? p + o : nullptr; o += align256(n); return r; };
-    w.ah = (_Float16*)take((size_t)Z * Lp * C * 2); w.al = (_Float16*)take((size_t)Z * Lp * C * 2);
-    w.bh = (_Float16*)take((size_t)Z * Sp * C * 2); w.bl = (_Float16*)take((size_t)Z * Sp * C * 2);
+    const int Lp = pad128(L), Sp = pad128(S);
+    Carver c{(unsigned char*)ws, 0};
+    w.ah = c.take<_Float16>((size_t)Z * Lp * C * 2); w.al = c.take<_Float16>((size_t)Z * Lp * C * 2);
+    w.bh = c.take<_Float16>((size_t)Z * Sp * C * 2); w.bl = c.take<_Float16>((size_t)Z * Sp * C * 2);
     const size_t nu = (size_t)(T + 1) * Z * Lp * 4, nv = (size_t)(T + 1) * Z * Sp * 4, nb = (size_t)(T + 1) * 2 * Z * 4;
-    w.uh = (float*)take(nu); w.vh = (float*)take(nv); w.binh = (float*)take(nb);
-    w.ubar = (float*)take(nu); w.vbar = (float*)take(nv); w.barbin = (float*)take(nb);
-    w.at = take((size_t)Z * (Lp / KB) * TILE_T);
-    w.bt = take((size_t)Z * (Sp / KB) * TILE_T);
+    w.uh = c.take<float>(nu); w.vh = c.take<float>(nv); w.binh = c.take<float>(nb);
+    w.ubar = c.take<float>(nu); w.vbar = c.take<float>(nv); w.barbin = c.take<float>(nb);
+    w.at = c.take((size_t)Z * (Lp / GT) * TILE_T);
+    w.bt = c.take((size_t)Z * (Sp / GT) * TILE_T);
     const int nt = 2 * T > 0 ? 2 * T : 1;
-    w.wl = (float*)take((size_t)nt * Z * Lp * 4); w.el = (float*)take((size_t)nt * Z * Lp * 4);
-    w.wsd = (float*)take((size_t)nt * Z * Sp * 4); w.es = (float*)take((size_t)nt * Z * Sp * 4);
-    w.wmax = (unsigned*)take((size_t)Z * 4);
-    w.sj0 = (int*)take((size_t)Z * Lp * KFOLD * 4); w.sj1 = (int*)take((size_t)Z * Sp * KFOLD * 4);
-    w.sw0 = (float*)take((size_t)Z * Lp * KFOLD * 4); w.sw1 = (float*)take((size_t)Z * Sp * KFOLD * 4);
-    w.part = (float*)take((size_t)Z * 4);
-    w.bytes = o;
+    w.wl = c.take<float>((size_t)nt * Z * Lp * 4); w.el = c.take<float>((size_t)nt * Z * Lp * 4);
+    w.wsd = c.take<float>((size_t)nt * Z * Sp * 4); w.es = c.take<float>((size_t)nt * Z * Sp * 4);
+    w.wmax = c.take<unsigned>((size_t)Z * 4);
+    w.sj0 = c.take<int>((size_t)Z * Lp * KFOLD * 4); w.sj1 = c.take<int>((size_t)Z * Sp * KFOLD * 4);
+    w.sw0 = c.take<float>((size_t)Z * Lp * KFOLD * 4); w.sw1 = c.take<float>((size_t)Z * Sp * KFOLD * 4);
+    w.part = c.take<float>((size_t)Z * 4);
+    w.bytes = c.o;
     return w;
 }
 
@@ -1010,17 +938,16 @@ struct WsD {                         // behind WsT in the workspace of the dense
 };
 inline WsD carve_d(void* ws, size_t o, int Z, int L, int S, int M) {
     WsD w;
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const int Lp = pad128(L), Sp = pad128(S);
     const size_t Mc = M > 0 ? M : 1;
-    unsigned char* p = (unsigned char*)ws;
-    auto take = [&](size_t n) { unsigned char* r = p ? p + o : nullptr; o += align256(n); return r; };
-    w.pr = (float*)take((size_t)Z * Lp * 4); w.pc = (float*)take((size_t)Z * Sp * 4);
-    w.u = (float*)take((size_t)Z * Lp * 4); w.v = (float*)take((size_t)Z * Sp * 4);
-    w.lossp = (double*)take((size_t)Z * (Lp / 128) * 8);
-    w.dl = (double*)take(Mc * 8);
-    w.dw = (float*)take(Mc * 4); w.wpos = (float*)take(Mc * 4);
-    w.gmax = (unsigned*)take((size_t)Z * 4);
-    w.bytes = o;
+    Carver c{(unsigned char*)ws, o};
+    w.pr = c.take<float>((size_t)Z * Lp * 4); w.pc = c.take<float>((size_t)Z * Sp * 4);
+    w.u = c.take<float>((size_t)Z * Lp * 4); w.v = c.take<float>((size_t)Z * Sp * 4);
+    w.lossp = c.take<double>((size_t)Z * (Lp / 128) * 8);
+    w.dl = c.take<double>(Mc * 8);
+    w.dw = c.take<float>(Mc * 4); w.wpos = c.take<float>(Mc * 4);
+    w.gmax = c.take<unsigned>((size_t)Z * 4);
+    w.bytes = c.o;
     return w;
 }
 
@@ -1033,20 +960,6 @@ int skt_backward(const WsT& w, const float* f0, const float* f1, int Z, int L, i
                  const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj, int M,
                  const float* w_pos, const float* w_bin0, const float* w_bin1, float* df0, float* df1, float* dbin, const DenseRun* dn,
                  hipStream_t stream);
-
-// the normalisers of a call (loftr_loss.py:63-70: without ground truth the positive term has weight 0 and every entry is a negative;
-// the labels handed over then only leave the negative term -- the caller passes the dummy entry (0, 0, 0) for a weighted batch)
-inline void make_plan(int Z, int L, int S, int M, float alpha, float gamma, float pos_weight, float neg_weight, int no_gt, FocalK& fk,
-                      double& cpos) {
-    const long npos = no_gt ? 0 : M;
-    const double nneg = (double)Z * (double)L * (double)S - (double)npos;
-    fk.alpha = alpha;
-    fk.gamma = gamma;
-    fk.cneg = nneg > 0 ? (float)((double)neg_weight / nneg) : 0.f;
-    fk.c_lo = -(double)alpha * pow(1e-6, (double)gamma) * log1p(-1e-6);
-    fk.c_hi = -(double)alpha * pow(1.0 - 1e-6, (double)gamma) * log(1e-6);
-    cpos = npos > 0 ? (double)pos_weight / (double)npos : 0.0;
-}
 
 }  // namespace
 
@@ -1066,7 +979,7 @@ int far_sinkhorn_pos_conf_f16s(const float* f0, const float* f1, int Z, int L, i
         (M > 0 && (!pb || !pi || !pj || !conf_pos)))
         return FAR_EINVAL;
     const WsT w = carve_t(ws, Z, L, S, iters);
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const int Lp = pad128(L), Sp = pad128(S);
     const int rc = far_skh_history_launch(f0, f1, Z, L, S, bin_score, iters, mask0, mask1, w.ah, w.al, w.bh, w.bl, w.uh, w.vh, w.binh,
                                           overflow, stream);
     if (rc != FAR_OK) return rc;
@@ -1090,7 +1003,7 @@ int far_sinkhorn_pos_conf_bwd_f16(const float* f0, const float* f1, int Z, int L
         (M > 0 && (!pb || !pi || !pj || !w_pos)))
         return FAR_EINVAL;
     const WsT w = carve_t(ws, Z, L, S, iters);
-    const int T = iters, Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const int T = iters, Lp = pad128(L), Sp = pad128(S);
     const size_t nu = (size_t)Z * Lp, nv = (size_t)Z * Sp;
     // ---- ubar^T = rowsum(G), vbar^T = colsum(G) without the positions
     hipLaunchKernelGGL(k_skt_seed, dim3(Z), dim3(256), 0, stream, w_bin0, w_bin1, Z, L, S, Lp, Sp, w.ubar + T * nu, w.vbar + T * nv,
@@ -1109,12 +1022,11 @@ int skt_backward(const WsT& w, const float* f0, const float* f1, int Z, int L, i
                  const uint8_t* mask0, const uint8_t* mask1, const int64_t* pb, const int64_t* pi, const int64_t* pj, int M,
                  const float* w_pos, const float* w_bin0, const float* w_bin1, float* df0, float* df1, float* dbin, const DenseRun* dn,
                  hipStream_t stream) {
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
+    const int Lp = pad128(L), Sp = pad128(S);
     const float c1 = (float)(1.4426950408889634 / ((double)C * PRESCALE * PRESCALE));
     const double n2 = -std::log2((double)L + (double)S);
     const float nrm = (float)n2, lmu_l = (float)(std::log2((double)S) + n2), lnu_s = (float)(std::log2((double)L) + n2);
     const size_t nu = (size_t)Z * Lp, nv = (size_t)Z * Sp;
-    auto gridp = [](long n) { long g = (n + 255) / 256; return (unsigned)(g < 16384 ? (g > 0 ? g : 1) : 16384); };
     const unsigned gpos = (unsigned)std::min((M + 3) / 4, 2048);
     if (M > 0)
         hipLaunchKernelGGL(k_skt_group<0>, dim3(gpos, 2), dim3(256), 0, stream, pb, pi, pj, w_pos, M, Z, L, S, Lp, Sp, mask0, mask1,
@@ -1156,8 +1068,8 @@ int skt_backward(const WsT& w, const float* f0, const float* f1, int Z, int L, i
             hipLaunchKernelGGL(k_skt_group<1>, dim3(gpos, 2), dim3(256), 0, stream, pb, pi, pj, w_pos, M, Z, L, S, Lp, Sp, mask0, mask1,
                                (float*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f, (float*)nullptr,
                                (float*)nullptr, (const unsigned*)w.wmax, KFOLD, T, w.sj0, w.sw0, w.sj1, w.sw1);
-        hipLaunchKernelGGL(k_skt_prep_t, dim3(gridp((long)Z * (Lp / KB) * C * 4)), dim3(256), 0, stream, f0, Z, L, Lp, mask0, w.at);
-        hipLaunchKernelGGL(k_skt_prep_t, dim3(gridp((long)Z * (Sp / KB) * C * 4)), dim3(256), 0, stream, f1, Z, S, Sp, mask1, w.bt);
+        hipLaunchKernelGGL(k1_prep_t, dim3(gridp((long)Z * (Lp / GT) * C * 4)), dim3(256), 0, stream, f0, Z, L, Lp, mask0, w.at);
+        hipLaunchKernelGGL(k1_prep_t, dim3(gridp((long)Z * (Sp / GT) * C * 4)), dim3(256), 0, stream, f1, Z, S, Sp, mask1, w.bt);
         const int nterm = 2 * T;
         const size_t smem = 2 * (size_t)(STAGE + nterm * 256 + (dn ? 256 : 0));
         const size_t smem_max = 2 * (size_t)(STAGE + 2 * MAX_ITERS * 256);
@@ -1225,24 +1137,24 @@ int far_sinkhorn_dense_focal_f16s(const float* f0, const float* f1, int Z, int L
         return FAR_EINVAL;
     const WsT w = carve_t(ws, Z, L, S, iters);
     const WsD d = carve_d(ws, w.bytes, Z, L, S, M);
-    const int Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
-    FocalK fk;
-    double cpos;
-    make_plan(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt, fk, cpos);
+    const int Lp = pad128(L), Sp = pad128(S);
+    // no_gt: every entry is a negative; the labels handed over then only leave the negative term (the caller passes the dummy entry
+    // (0, 0, 0) for a weighted batch)
+    const FocalPlan pl = make_plan(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt);
+    const FocalK& fk = pl.fk;
     const int rc = far_skh_history_launch(f0, f1, Z, L, S, bin_score, iters, mask0, mask1, w.ah, w.al, w.bh, w.bl, w.uh, w.vh, w.binh,
                                           overflow, stream);
     if (rc != FAR_OK) return rc;
     const float c1 = (float)(1.4426950408889634 / ((double)C * PRESCALE * PRESCALE));
     const float nrm = (float)(-std::log2((double)L + (double)S));
-    auto gridp = [](long n) { long g = (n + 255) / 256; return (unsigned)(g < 16384 ? (g > 0 ? g : 1) : 16384); };
     hipLaunchKernelGGL(k_skd_side, dim3(gridp((long)Z * (Lp + Sp))), dim3(256), 0, stream, (const float*)(w.uh + (size_t)iters * Z * Lp),
                        (const float*)(w.vh + (size_t)iters * Z * Sp), mask0, mask1, Z, L, S, Lp, Sp, nrm, d.pr, d.pc);
     hipMemsetAsync(d.gmax, 0, (size_t)Z * 4, stream);
     if (M > 0)
         hipLaunchKernelGGL(k_skd_pos, dim3(std::min((M + 127) / 128, 2048)), dim3(256), 0, stream, (const _Float16*)w.ah, (const _Float16*)w.al,
                            (const _Float16*)w.bh, (const _Float16*)w.bl, Z, L, S, Lp, Sp, c1, pb, pi, pj, M, (const float*)d.pr,
-                           (const float*)d.pc, fk, cpos, d.dl, d.dw, d.gmax);
-    const size_t smem = 2 * (2 * PLANE32) + 2 * DT * sizeof(float);
+                           (const float*)d.pc, fk, pl.cpos, d.dl, d.dw, d.gmax);
+    const size_t smem = 2 * (2 * PLANE32) + 2 * GT * sizeof(float);
     FAR_ONCE_PER_DEVICE(hipFuncSetAttribute((const void*)k_skd_pass<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
                         hipFuncSetAttribute((const void*)k_skd_pass<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     const int nparts = (Lp / 128) * Z;
@@ -1252,7 +1164,7 @@ int far_sinkhorn_dense_focal_f16s(const float* f0, const float* f1, int Z, int L
     hipLaunchKernelGGL(k_skd_pass<false>, dim3((Sp / 128) * Z), dim3(256), smem, stream, (const _Float16*)w.bh, (const _Float16*)w.bl,
                        (const _Float16*)w.ah, (const _Float16*)w.al, Z, S, L, Sp, Lp, c1, (const float*)d.pc, (const float*)d.pr, d.v, fk,
                        (unsigned*)nullptr, (double*)nullptr);
-    hipLaunchKernelGGL(k_skd_loss, dim3(1), dim3(256), 0, stream, (const double*)d.lossp, nparts, (const double*)d.dl, M, (double)fk.cneg,
+    hipLaunchKernelGGL(k1_focal_loss, dim3(1), dim3(256), 0, stream, (const double*)d.lossp, nparts, (const double*)d.dl, M, (double)fk.cneg,
                        loss_out);
     return far_check_launch();
 }
@@ -1267,10 +1179,8 @@ int far_sinkhorn_dense_focal_bwd_f16(const float* f0, const float* f1, int Z, in
         return FAR_EINVAL;
     const WsT w = carve_t(ws, Z, L, S, iters);
     const WsD d = carve_d(ws, w.bytes, Z, L, S, M);
-    const int T = iters, Lp = (L + 127) / 128 * 128, Sp = (S + 127) / 128 * 128;
-    FocalK fk;
-    double cpos;
-    make_plan(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt, fk, cpos);
+    const int T = iters, Lp = pad128(L), Sp = pad128(S);
+    const FocalK fk = make_plan(Z, L, S, M, alpha, gamma, pos_weight, neg_weight, no_gt).fk;
     hipLaunchKernelGGL(k_skd_seed, dim3(Z), dim3(256), 0, stream, (const float*)d.u, (const float*)d.v, (const float*)d.dw, M, gup, Z, Lp, Sp,
                        w.ubar + (size_t)T * Z * Lp, w.vbar + (size_t)T * Z * Sp, w.barbin + (size_t)T * 2 * Z, d.wpos);
     const DenseRun dn{d.pr, d.pc, gup, d.gmax, fk.cneg, fk.alpha, fk.gamma};

@@ -103,6 +103,43 @@ def test_dense_abi_is_bound_and_the_workspace_holds_no_matrix():
     assert lib.far_coarse_dense_focal_workspace_bytes(1, 35, 72, 256, 0) > 0
 
 
+# The workspace sizes of the four K1 training families at (Z, L, S), C = 256, as literals: the forward call leaves its planes and
+# statistics in the workspace for the backward call, so the carving (k1_train_f16s.h: Carver, pad128) must not drift.
+K1_SHAPES = [(1, 35, 72), (2, 48, 48), (1, 130, 70), (3, 192, 192), (32, 4800, 4800)]
+K1_M = (0, 1500)
+K1_T = (0, 3, 48)
+COARSE_TRAIN_WS = [440832, 873216, 658944, 2659072, 610579456]
+COARSE_DENSE_WS = [(441856, 459520), (875008, 892672), (659968, 677632), (2661376, 2679040), (610606080, 610623744)]       # [shape][M]
+SINKHORN_POS_WS = [(439296, 455680, 732672), (877568, 910336, 1464832), (658432, 683008, 1098240), (2630656, 2728960, 4389888),
+                   (532939776, 552864256, 889086976)]                                                                        # [shape][T]
+SINKHORN_DENSE_WS = [((442624, 466176), (459008, 482560), (736000, 759552)),                                                 # [shape][T][M]
+                     ((882944, 906496), (915712, 939264), (1470208, 1493760)),
+                     ((662784, 686336), (687360, 710912), (1102592, 1126144)),
+                     ((2644224, 2667776), (2742528, 2766080), (4403456, 4427008)),
+                     ((535440896, 535464448), (555365376, 555388928), (891588096, 891611648))]
+
+
+def test_k1_training_workspace_sizes_are_pinned():
+    lib = _lib.load()
+    for n, (Z, L, S) in enumerate(K1_SHAPES):
+        assert lib.far_coarse_train_workspace_bytes(Z, L, S, 256) == COARSE_TRAIN_WS[n], (Z, L, S)
+        for m, M in enumerate(K1_M):
+            assert lib.far_coarse_dense_focal_workspace_bytes(Z, L, S, 256, M) == COARSE_DENSE_WS[n][m], (Z, L, S, M)
+        for t, T in enumerate(K1_T):
+            assert lib.far_sinkhorn_pos_conf_workspace_bytes(Z, L, S, 256, T) == SINKHORN_POS_WS[n][t], (Z, L, S, T)
+            for m, M in enumerate(K1_M):
+                assert lib.far_sinkhorn_dense_focal_workspace_bytes(Z, L, S, 256, T, M) == SINKHORN_DENSE_WS[n][t][m], (Z, L, S, T, M)
+    # the refusals: another width, an empty batch, a negative label count, more iterations than the staged column terms allow
+    assert lib.far_coarse_train_workspace_bytes(1, 35, 72, 128) == 0 and lib.far_coarse_train_workspace_bytes(0, 35, 72, 256) == 0
+    assert lib.far_coarse_dense_focal_workspace_bytes(1, 35, 72, 128, 0) == 0 and lib.far_coarse_dense_focal_workspace_bytes(0, 35, 72, 256, 0) == 0
+    assert lib.far_coarse_dense_focal_workspace_bytes(1, 35, 72, 256, -1) == 0
+    assert lib.far_sinkhorn_pos_conf_workspace_bytes(1, 35, 72, 128, 3) == 0 and lib.far_sinkhorn_pos_conf_workspace_bytes(0, 35, 72, 256, 3) == 0
+    assert lib.far_sinkhorn_pos_conf_workspace_bytes(1, 35, 72, 256, 49) == 0
+    assert lib.far_sinkhorn_dense_focal_workspace_bytes(1, 35, 72, 128, 3, 0) == 0 and lib.far_sinkhorn_dense_focal_workspace_bytes(0, 35, 72, 256, 3, 0) == 0
+    assert lib.far_sinkhorn_dense_focal_workspace_bytes(1, 35, 72, 256, 3, -1) == 0
+    assert lib.far_sinkhorn_dense_focal_workspace_bytes(1, 35, 72, 256, 49, 0) == 0
+
+
 def test_op_refuses_cpu_tensors_and_other_widths():
     from far_amd import ops
     ids = torch.zeros(1, dtype=torch.long)

@@ -1,7 +1,8 @@
-"""Same-box A/B of output BITS: runs K22 (ops.full_attention_train) and K23 (ops.vit_attention_train, vit_attention_train_qkv) forward
-and backward on seeded inputs with far_amd/lib/libfar_hip_base.so (tools/ab_build.py) and with the working tree's library, each in a
-fresh child process, and compares the sha256 of every output (out, lse, dq, dk, dv).  The kernels are deterministic and built with
--ffp-contract=off: a refactor that keeps every expression gives equal digests; a difference names the case and the tensor.
+"""Same-box A/B of output BITS: runs K22 (ops.full_attention_train), K23 (ops.vit_attention_train, vit_attention_train_qkv) and the
+K1 training ops (ops.coarse_pos_conf, coarse_dense_focal_loss, sinkhorn_pos_conf, sinkhorn_dense_focal_loss) forward and backward
+on seeded inputs with far_amd/lib/libfar_hip_base.so (tools/ab_build.py) and with the working tree's library, each in a fresh child
+process, and compares the sha256 of every output (out, lse, dq, dk, dv; values, loss, df0, df1, dbin).  The kernels are deterministic
+and built with -ffp-contract=off: a refactor that keeps every expression gives equal digests; a difference names the case and the tensor.
 Usage: python tools/ab_build.py [rev] && python tools/ab_outputs.py      (exit status 1 on any difference or a failed child)"""
 import hashlib
 import json
@@ -17,6 +18,70 @@ K22 = [(2, 300, 1200, 8, 32), (2, 1200, 300, 8, 32), (2, 200, 150, 8, 32), (3, 2
 K22_VALID = {(2, 130, 70, 3, 16): ((90, 130), (70, 33))}          # valid query / key prefix per image (tests: case t7)
 # K23 (Z, L, S, H); the last one also as one packed (Z, N, 3 H 64) qkv projection
 K23 = [(2, 130, 65, 3), (2, 33, 40, 3), (2, 576, 576, 3), (2, 130, 130, 3)]
+
+# K1 training (Z, L, S): one whole tile; the other two straddle the 32-column tile and the 128-row padding.  Each runs without and
+# with padded masks (coarse_pos_conf takes none).  K1_T: skt_backward's dispatch -- T = 0 (no dense part), 2 T <= 6 (k_skt_bwd<6>),
+# <= 12 (<12>, sparse only), beyond (<0>); the dense forms have <6, .> (also at T = 0) and <0, .>.
+K1 = [(2, 48, 48), (1, 35, 72), (1, 130, 70)]
+K1_T = {'sparse': (0, 2, 5, 8), 'dense': (0, 2, 8)}
+K1_FOCAL = (0.25, 2.0, 0.3, 300.0)                 # alpha, gamma, pos_weight, neg_weight: the dense negative part carries the gradient
+
+
+def k1_case(np, torch, Z, L, S, amp, seed):
+    """f1 = noisy copies of f0's rows at permuted columns (confident matches next to entries far below the clamp); `one`: labels with
+    pairwise distinct rows and columns per image (coarse_pos_conf adds u, v with float atomics: one addend per sum); `multi`: the same
+    plus six positions on one row of image 0 (more than KFOLD); masks: valid prefixes that differ per image."""
+    rng = np.random.default_rng(seed)
+    f0 = (amp * rng.standard_normal((Z, L, 256))).astype(np.float32)
+    f1 = (amp * rng.standard_normal((Z, S, 256))).astype(np.float32)
+    K = min(L, S) - 3
+    b, i, j = [], [], []
+    for z in range(Z):
+        rows, cols = rng.permutation(L)[:K], rng.permutation(S)[:K]
+        f1[z, cols] = f0[z, rows] + 0.02 * rng.standard_normal((K, 256)).astype(np.float32)
+        keep = rng.permutation(K)[:int(0.7 * K)]
+        b += [z] * len(keep); i += rows[keep].tolist(); j += cols[keep].tolist()
+    ids = lambda *a: tuple(torch.tensor(x, dtype=torch.int64).cuda() for x in a)
+    one = ids(b, i, j)
+    extra = rng.permutation(S)[:6].tolist()
+    multi = ids(b + [0] * 6, i + [i[0]] * 6, j + extra)
+    m0 = torch.arange(L)[None] < torch.tensor([L - 5 - 2 * z for z in range(Z)])[:, None]
+    m1 = torch.arange(S)[None] < torch.tensor([S - 3 - z for z in range(Z)])[:, None]
+    return torch.from_numpy(f0).cuda(), torch.from_numpy(f1).cuda(), one, multi, (m0.cuda(), m1.cuda())
+
+
+def k1_training(np, torch, ops, emit):
+    from far_amd.ops import coarse
+    for n, (Z, L, S) in enumerate(K1):
+        f0, f1, one, multi, masks = k1_case(np, torch, Z, L, S, 2.0, 400 + n)
+        g0, g1, a0 = k1_case(np, torch, Z, L, S, 3.75, 500 + n)[:2] + (torch.tensor(1.0).cuda(),)         # the Sinkhorn operands
+        rng = np.random.default_rng(600 + n)
+        up = lambda *shape: torch.from_numpy(np.asarray(rng.standard_normal(shape), np.float32)).cuda()      # upstream gradients
+        leaf = lambda *ts: tuple(t.detach().clone().requires_grad_() for t in ts)
+        x0, x1 = leaf(f0, f1)
+        p = ops.coarse_pos_conf(x0, x1, *one, 0.1)
+        emit(f'K1 pos_conf {(Z, L, S)}', ('values', 'df0', 'df1'), (p.detach(),) + torch.autograd.grad(p, (x0, x1), up(p.numel())))
+        for mm in ((None, None), masks):
+            tag = f'{(Z, L, S)}{" masked" if mm[0] is not None else ""}'
+            for split_g in (True, False):
+                for no_gt in ((False, True) if n == 0 else (False,)):
+                    coarse.DENSE_FOCAL_SPLIT_G = split_g
+                    x0, x1 = leaf(f0, f1)
+                    loss = ops.coarse_dense_focal_loss(x0, x1, *multi, 0.1, *K1_FOCAL, *mm, no_gt=no_gt)
+                    emit(f'K1 dense_focal {tag} split_g={split_g} no_gt={no_gt}', ('loss', 'df0', 'df1'),
+                         (loss.detach(),) + torch.autograd.grad(loss, (x0, x1), up()))
+            coarse.DENSE_FOCAL_SPLIT_G = True
+            for T in K1_T['sparse']:
+                x0, x1, a = leaf(g0, g1, a0)
+                out = ops.sinkhorn_pos_conf(x0, x1, a, T, *multi, *mm)
+                grads = torch.autograd.grad(out, (x0, x1, a), tuple(up(*o.shape) for o in out))
+                emit(f'K1 sinkhorn_pos_conf {tag} T={T}', ('values', 'bin0', 'bin1', 'df0', 'df1', 'dbin'), tuple(o.detach() for o in out) + grads)
+            for T in K1_T['dense']:
+                for no_gt in ((False, True) if n == 0 and T == 2 else (False,)):
+                    x0, x1, a = leaf(g0, g1, a0)
+                    loss = ops.sinkhorn_dense_focal_loss(x0, x1, a, T, *multi, *K1_FOCAL, *mm, no_gt=no_gt)
+                    emit(f'K1 sinkhorn_dense_focal {tag} T={T} no_gt={no_gt}', ('loss', 'df0', 'df1', 'dbin'),
+                         (loss.detach(),) + torch.autograd.grad(loss, (x0, x1, a), up()))
 
 
 def child():
@@ -60,6 +125,7 @@ def child():
     lse = out.grad_fn.saved_tensors[-1]
     dqkv, = torch.autograd.grad(out, (qkv,), g)
     emit(f'K23 packed {(Z, N, N, H)}', names, (out.detach(), lse) + tuple(dqkv[..., j * H * 64:(j + 1) * H * 64] for j in range(3)))
+    k1_training(np, torch, ops, emit)
     if ops.activation_overflowed('cuda'):
         sys.exit('the overflow flag is set: the inputs left the split range')
 
