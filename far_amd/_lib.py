@@ -151,6 +151,10 @@ SIGNATURES = {
     'far_conv_valid_packed_bytes': (c_sz, [c_i, c_i, c_i]),
     'far_conv_valid_pack_f32': (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     'far_conv_valid_f16s': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),     # K24
+    'far_conv_valid_pack_dgrad_f32': (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
+    'far_conv_valid_dgrad_f16s': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),                  # K24 backward
+    'far_conv_valid_wgrad_ws_bytes': (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),
+    'far_conv_valid_wgrad_f16s': (c_i, [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_l, c_p, c_p, c_p]),
     'far_stem_rgb_packed_bytes': (c_sz, []),
     'far_stem_rgb_pack_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p]),
     'far_stem_rgb_f16s': (c_i, [c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),                              # K25

@@ -521,6 +521,104 @@ def conv_valid(x, pack, residual=None, act='none'):
     _lib.check(rc, 'far_conv_valid_f16s')
     return y
 
+def _valid_bwd_shapes(what, x_shape, dy, Cin, Cout):
+    """(N, H, W) of a K24 backward launch; FarHipError for anything far_conv_valid_f16s would not have produced dy from."""
+    if not dy.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if len(x_shape) != 4 or dy.dim() != 4:
+        raise _lib.FarHipError(f'{what}: NHWC tensors expected, got x {tuple(x_shape)} and dy {tuple(dy.shape)}')
+    N, H, W, _ = x_shape
+    if Cin % 32 or Cout % 32 or Cin <= 0 or Cout <= 0:
+        raise _lib.FarHipError(f'{what}: K24 covers Cin and Cout multiples of 32, got {Cin} -> {Cout}')
+    if H < 5 or W < 5:
+        raise _lib.FarHipError(f'{what}: a {H} x {W} input is smaller than the 5 x 5 kernel')
+    if tuple(dy.shape) != (N, H - 4, W - 4, Cout):
+        raise _lib.FarHipError(f'{what}: dy of shape {tuple(dy.shape)}, expected {(N, H - 4, W - 4, Cout)}')
+    return N, H, W
+
+def conv_valid_dgrad(dy, weight_or_pack, dy_scale=None):
+    """K24 dgrad.  dy (N, H - 4, W - 4, Cout) fp32 NHWC -> dx (N, H, W, Cin), the input gradient of conv5x5_valid with the weight
+    (Cout, Cin, 5, 5) or its PackedConvValid(dgrad=True) image; dy_scale = grad_scale(dy) if the caller has it already."""
+    lib = _lib.load()
+    if isinstance(weight_or_pack, PackedConvValid):
+        pack = weight_or_pack
+        if not pack.dgrad:
+            raise _lib.FarHipError('conv_valid_dgrad takes a PackedConvValid built with dgrad=True')
+    else:
+        w = weight_or_pack
+        if w.dim() != 4 or tuple(w.shape[2:]) != (5, 5):
+            raise _lib.FarHipError(f'conv_valid_dgrad takes a (Cout, Cin, 5, 5) weight, got {tuple(w.shape)}')
+        pack = PackedConvValid(w, dgrad=True, pack_scale=PackedConvValid(w).pack_scale)
+    if dy.dim() != 4:
+        raise _lib.FarHipError(f'conv_valid_dgrad: NHWC dy expected, got {tuple(dy.shape)}')
+    N, H, W = _valid_bwd_shapes('conv_valid_dgrad', (dy.shape[0], dy.shape[1] + 4, dy.shape[2] + 4, pack.Cin), dy, pack.Cin, pack.Cout)
+    dy = dy.contiguous()
+    sc = grad_scale(dy) if dy_scale is None else dy_scale
+    dx = torch.empty(N, H, W, pack.Cin, dtype=torch.float32, device=dy.device)
+    rc = lib.far_conv_valid_dgrad_f16s(_p(dy, torch.float32), _p(pack.packed), _p(pack.pack_scale), _p(sc, torch.float32), _p(dx), N, H, W,
+                                       pack.Cin, pack.Cout, pack.ksize, overflow_flag(dy.device).data_ptr(), _stream())
+    _lib.check(rc, 'far_conv_valid_dgrad_f16s')
+    return dx
+
+def conv_valid_wgrad(x, dy, dy_scale=None, act_exp=None):
+    """K24 wgrad.  dW (Cout, Cin, 5, 5) of conv5x5_valid from its NHWC input x (N, H, W, Cin) and output gradient dy (N, H - 4, W - 4,
+    Cout); deterministic two-stage sum.  act_exp: the activation exponent x was consumed with in the forward (default: the current
+    one); takes part in the activation-range guard."""
+    lib = _lib.load()
+    if not x.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    Cin, Cout = int(x.shape[-1]), int(dy.shape[-1])
+    N, H, W = _valid_bwd_shapes('conv_valid_wgrad', tuple(x.shape), dy, Cin, Cout)
+    x, dy = x.contiguous(), dy.contiguous()
+    dw = torch.empty(Cout, Cin, 5, 5, dtype=torch.float32, device=x.device)
+    if N == 0:
+        return dw.zero_()
+    nb = int(lib.far_conv_valid_wgrad_ws_bytes(N, H, W, Cin, Cout, 5))
+    ws = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    rc = lib.far_conv_valid_wgrad_f16s(_p(x, torch.float32), _p(dy, torch.float32), N, H, W, Cin, Cout, 5,
+                                       activation_exponent_value() if act_exp is None else int(act_exp),
+                                       _p(dy_scale, torch.float32) if dy_scale is not None else None, _p(ws), nb, _p(dw),
+                                       overflow_flag(x.device).data_ptr(), _stream())
+    _lib.check(rc, 'far_conv_valid_wgrad_f16s')
+    return dw
+
+class _ConvValidFn(torch.autograd.Function):
+    """The bare 5x5 unpadded convolution of the extractor's final block with gradients (extractor.py:11, :46-47 under autograd, without
+    the bias): forward K24, backward far_conv_valid_dgrad_f16s / far_conv_valid_wgrad_f16s.  NHWC in and out."""
+
+    @staticmethod
+    def forward(ctx, x, weight, pack, pack_d):
+        xn = x.detach().float().contiguous()
+        y = conv_valid(xn, pack())
+        ctx.save_for_backward(xn, weight)
+        ctx.pack_d = pack_d
+        ctx.act_exp = activation_exponent_value()            # the weight gradient splits xn with the forward's exponent
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        xn, weight = ctx.saved_tensors
+        gs = g.float().contiguous()
+        sc = grad_scale(gs)
+        dx = conv_valid_dgrad(gs, ctx.pack_d(), dy_scale=sc) if ctx.needs_input_grad[0] else None
+        dw = conv_valid_wgrad(xn, gs, dy_scale=sc, act_exp=ctx.act_exp) if ctx.needs_input_grad[1] else None
+        return dx, dw, None, None
+
+def conv_valid_train(x, weight, cache, name):
+    """K24 with gradients.  x (N, H, W, Cin) fp32 GPU, NHWC; weight (Cout, Cin, 5, 5); cache: a PackCache.  Returns the bare
+    convolution (N, H - 4, W - 4, Cout), NHWC.  The images are re-packed in place after an optimizer step, as conv_train's."""
+    if not x.is_cuda or not weight.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (5, 5) or x.dim() != 4 or x.shape[-1] != weight.shape[1]:
+        raise _lib.FarHipError(f'conv_valid_train: x {tuple(x.shape)} (NHWC) and weight {tuple(weight.shape)} are no 5x5 convolution')
+    if x.shape[1] < 5 or x.shape[2] < 5:
+        raise _lib.FarHipError(f'conv_valid_train: a {x.shape[1]} x {x.shape[2]} input is smaller than the 5 x 5 kernel')
+    re = lambda pc: pc.refresh(weight)                 # the forward image first: the dgrad image borrows its (refreshed) scale
+    pack = lambda: cache.get((name, 'valid'), [weight], lambda: PackedConvValid(weight), refresh=re)
+    pack_d = lambda: cache.get((name, 'valid', 'dgrad'), [weight], lambda: PackedConvValid(weight, dgrad=True, pack_scale=pack().pack_scale),
+                               refresh=re).follow_scale(pack(), weight)
+    return _ConvValidFn.apply(x, weight, pack, pack_d)
+
 _RESIZE_TABLES = {}
 
 def resize_tables(H, W, device, size=224):

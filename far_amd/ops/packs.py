@@ -152,42 +152,61 @@ class PackedWino:
 class PackedConvValid:
     """Weights of one K x K unpadded stride-1 convolution (K = 5) in K24's packed split-fp16 image, plus the folded epilogue vectors:
     the same constructor meaning as PackedConv (scale / shift: the inference BatchNorm as a per-channel affine map, a convolution
-    bias folded into shift by the caller)."""
+    bias folded into shift by the caller).  dgrad=True packs the image of the layer's input-gradient convolution -- channels
+    exchanged, taps reversed -- with pack_scale, the two device floats of the forward image of the same weight."""
 
     stride, split = 1, True
 
-    def __init__(self, weight, scale=None, shift=None):
+    def __init__(self, weight, scale=None, shift=None, dgrad=False, pack_scale=None):
         lib = _lib.load()
         w = weight.detach()
         if w.dim() != 4 or w.shape[2] != w.shape[3]:
             raise _lib.FarHipError(f'K24 takes a (Cout, Cin, k, k) weight, got {tuple(w.shape)}')
         if not w.is_cuda:
             raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+        if dgrad and (pack_scale is None or scale is not None or shift is not None):
+            raise _lib.FarHipError("K24's dgrad image borrows the forward image's pack_scale and has no epilogue vectors")
+        if not dgrad and pack_scale is not None:
+            raise _lib.FarHipError("K24's forward image computes its own pack_scale")
         w = w.contiguous().float()
-        self.Cout, self.Cin, self.ksize = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+        self.Cout, self.Cin, self.ksize, self.dgrad = int(w.shape[0]), int(w.shape[1]), int(w.shape[2]), bool(dgrad)
         nbytes = int(lib.far_conv_valid_packed_bytes(self.Cin, self.Cout, self.ksize))
         if nbytes == 0:
             raise _lib.FarHipError(f'K24 (far_conv_valid_f16s) covers 5x5 kernels with Cin and Cout multiples of 32, got a weight of shape '
                                    f'{tuple(w.shape)}')
         self.packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-        self.pack_scale = torch.empty(2, dtype=torch.float32, device=w.device)       # { 2^w_exp, 2^-(w_exp + 4) }
+        self._own_scale = not dgrad
+        self.pack_scale = torch.empty(2, dtype=torch.float32, device=w.device) if not dgrad else pack_scale   # { 2^w_exp, 2^-(w_exp + 4) }
         self._base = None if scale is None else scale.detach().float().contiguous()
-        self.scale = torch.empty(self.Cout, dtype=torch.float32, device=w.device)
+        self.scale = None if dgrad else torch.empty(self.Cout, dtype=torch.float32, device=w.device)
         self.shift = None if shift is None else shift.detach().float().contiguous()
         self._wshape = tuple(w.shape)
         self.refresh(w)
 
     def refresh(self, weight):
-        """(Re-)packs the image from `weight` into the same buffers: two launches, no allocation, no host read."""
+        """(Re-)packs the image from `weight` into the same buffers: two launches (a dgrad image: one, after its forward image's
+        refresh), no allocation, no host read."""
         lib = _lib.load()
         w = weight.detach()
         if tuple(w.shape) != self._wshape or w.dtype != torch.float32 or not w.is_contiguous() or w.device != self.packed.device:
             raise _lib.FarHipError('PackedConvValid.refresh: the weight changed shape, dtype, layout or device')
-        _lib.check(lib.far_weight_scale_f32(_p(w, torch.float32), w.numel(), _p(self.pack_scale), _stream()), 'far_weight_scale_f32')
-        rc = lib.far_conv_valid_pack_f32(_p(w), self.Cin, self.Cout, self.ksize, _p(self.pack_scale), _p(self.packed),
-                                         _p(self._base) if self._base is not None else None, _p(self.scale), _stream())
-        _lib.check(rc, 'far_conv_valid_pack_f32')
+        if self.dgrad:
+            rc = lib.far_conv_valid_pack_dgrad_f32(_p(w), self.Cin, self.Cout, self.ksize, _p(self.pack_scale), _p(self.packed), _stream())
+            _lib.check(rc, 'far_conv_valid_pack_dgrad_f32')
+        else:
+            _lib.check(lib.far_weight_scale_f32(_p(w, torch.float32), w.numel(), _p(self.pack_scale), _stream()), 'far_weight_scale_f32')
+            rc = lib.far_conv_valid_pack_f32(_p(w), self.Cin, self.Cout, self.ksize, _p(self.pack_scale), _p(self.packed),
+                                             _p(self._base) if self._base is not None else None, _p(self.scale), _stream())
+            _lib.check(rc, 'far_conv_valid_pack_f32')
         self._w = w
+        return self
+
+    def follow_scale(self, owner, weight):
+        """A dgrad image whose forward image was REBUILT rather than refreshed rebinds to the new scale tensor and re-packs (as
+        PackedConv.follow_scale).  Returns self."""
+        if not self._own_scale and self.pack_scale.data_ptr() != owner.pack_scale.data_ptr():
+            self.pack_scale = owner.pack_scale
+            self.refresh(weight)
         return self
 
 class PackedStemRGB:

@@ -18,10 +18,15 @@ The extractor (model.py:56-60, :131-163; modules/extractor.py:5-65) is opt-in: `
 as nn.Conv2d / nn.BatchNorm2d modules -- reference_state_dict(sd, extractor=True) then drops only resnet.layer3.* / layer4.* -- and
 `forward(images)` / `extract_features(images)` run it in 14 launches: K25 (ops.stem_rgb: channel flip, / 255, normalisation, nearest
 resize to 224, conv1, bn1, relu), K26 (ops.maxpool3x3s2), K9 / K17 (ops.conv_nhwc: layer1, layer2, extractor_final_conv.conv1) and
-K24 (ops.conv_valid: the two 5x5 unpadded convolutions with the block's add and ReLUs).  It is inference-only and FROZEN, which the
-reference's is not (it fine-tunes these layers): requires_grad False on its parameters, running statistics in every BatchNorm
-whatever .train() says, detached features under set_block_training(); an extractor parameter with requires_grad=True raises when
-gradients are enabled.  Without the keyword nothing changes: no such submodules, and forward(images) raises as before.
+K24 (ops.conv_valid: the two 5x5 unpadded convolutions with the block's add and ReLUs).  By default it is inference-only and FROZEN,
+which the reference's is not (it fine-tunes these layers): requires_grad False on its parameters, running statistics in every
+BatchNorm whatever .train() says, detached features under set_block_training(); an extractor parameter with requires_grad=True
+raises when gradients are enabled.  Without the keyword nothing changes: no such submodules, and forward(images) raises as before.
+`ViTEss.set_extractor_training()` opts in to fine-tuning extractor_final_conv (the reference's ResidualBlock(128, 192, 'batch',
+kernel_size=5), half of the extractor's arithmetic) with the trunk: in .train() mode under enabled gradients the block runs on
+K9 + K16 (conv1), K24 forward + its HIP backward (ops.conv_valid_train: conv2, downsample.0) and K19 (the three BatchNorm layers with
+batch statistics, running statistics updated as nn.BatchNorm2d does), and the features carry gradients.  The ResNet front stays
+frozen on its running statistics (a deviation: the reference's whole model is in .train()); gradients into resnet.* raise.
 
 Training (the reference's train.py: MSE on the translation plus MSE on the rotation output, clip_grad_norm_, AdamW) is opt-in,
 modelled on LoFTR.set_full_attention_training(): `ViTEss.set_block_training()` sets `block_training` on the trunk, its Blocks and
@@ -32,7 +37,7 @@ GELU and the residual adds are elementwise torch ops.  The CrossBlock trains on 
 containers run under autograd (the package's convention for them, far_amd/_vendor.py).  `pose_loss` is the reference's loss;
 far_amd.optim (K20) is the optimizer side.  The no-grad path is the same code and the same bits whatever the switch says.
 
-Not built (each raises NotImplementedError): extractor training, dropout and drop-path (0 in every script), per-sample intrinsics, and
+Not built (each raises NotImplementedError): training the extractor's ResNet front (K25 / K26 have no backward), dropout and drop-path (0 in every script), per-sample intrinsics, and
 the pooled-conv ablation (fusion_transformer=False).
 
 Pair order: the reference keeps the two images of pair b in rows 2b, 2b + 1 of a (2B, N, C) tensor; this package's CrossBlock takes
@@ -324,7 +329,7 @@ class ViTEss(nn.Module):
         super().__init__()
         self.has_extractor = bool(extractor)
         if self.has_extractor:
-            # model.py:58-60 under the reference's names; inference-only and frozen in this package (the reference fine-tunes them)
+            # model.py:58-60 under the reference's names; frozen here (the reference fine-tunes them) until set_extractor_training()
             self.resnet = _ResNetFront()
             self.extractor_final_conv = _FinalConv()
             self.resnet.requires_grad_(False)
@@ -364,6 +369,37 @@ class ViTEss(nn.Module):
                 blk.block_training = blk.attn.block_training = on
         return self
 
+    def set_extractor_training(self, part='final', on=True):
+        """Opt in to (or out of) fine-tuning the extractor's final block (extractor_final_conv, half of the extractor's arithmetic)
+        with the trunk: sets the plain attribute `extractor_training` and requires_grad on the extractor_final_conv.* parameters; the
+        state dict's keys do not change.  In .train() mode under enabled gradients extract_features then runs the block on the
+        training kernels (batch statistics, K9 + K16, K24 forward + backward, K19) and its output carries gradients; the ResNet front
+        stays frozen on its running statistics.  Returns self."""
+        if not self.has_extractor:
+            raise self._no_extractor()
+        if part != 'final':
+            raise NotImplementedError(f"ViTEss.set_extractor_training(part={part!r}): only part='final' (extractor_final_conv) trains; "
+                                      'gradients into resnet.* need backward kernels for K25 (far_stem_rgb_f16s) and K26 '
+                                      '(far_maxpool3x3s2_nhwc_f32), which do not exist')
+        self.extractor_training = bool(on)
+        self.extractor_final_conv.requires_grad_(bool(on))
+        return self
+
+    def _final_block_train(self, x):
+        """extractor.py:51-65 in training mode with gradients: x (N, H, W, 128) NHWC fp32 -> (N, H - 4, W - 4, 192) NHWC.  conv1 on K9 +
+        K16 (ops.conv_train), conv2 / downsample.0 on K24 forward + backward (ops.conv_valid_train), the three BatchNorm layers with
+        batch statistics on K19 (ops.bn_act_train: norm3 takes the block's add and final ReLU); the convolution biases are torch
+        elementwise adds in front of the BatchNorm (running_mean then equals the module's; their gradients come from autograd)."""
+        fc = self.extractor_final_conv
+        pk = self.__dict__.setdefault('_extractor_train_packs', ops.PackCache())
+        nchw = lambda t: t.permute(0, 3, 1, 2)                       # NHWC tensor -> (N, C, H, W) logical, channels_last memory
+        y = ops.conv_train(nchw(x), fc.conv1.weight, 1, pk, 'final.conv1') + fc.conv1.bias.view(1, -1, 1, 1)
+        y = ops.bn_act_train(y, fc.norm1, act='relu')                                                    # extractor.py:53
+        y = ops.conv_valid_train(y.permute(0, 2, 3, 1), fc.conv2.weight, pk, 'final.conv2') + fc.conv2.bias
+        y = ops.bn_act_train(nchw(y), fc.norm2, act='relu')                                              # :54
+        d = ops.conv_valid_train(x, fc.downsample[0].weight, pk, 'final.downsample') + fc.downsample[0].bias
+        return ops.bn_act_train(nchw(d), fc.norm3, act='relu', residual=y).permute(0, 2, 3, 1)           # :56-57, :65
+
     def _no_extractor(self):
         return NotImplementedError('ViTEss.forward(images): the extractor (torchvision ResNet18 conv1 .. layer2 + ResidualBlock, '
                                    'model.py:131-163) is not built -- torchvision is not a dependency of this package.  Run it '
@@ -396,15 +432,33 @@ class ViTEss(nn.Module):
         b, intrinsics on the 24 x 24 grid (update_intrinsics with the ORIGINAL image size; None stays None)).  14 launches: K25 (flip,
         normalisation, resize to 224, conv1, bn1, relu), K26 (maxpool), K9 / K17 (layer1, layer2, extractor_final_conv.conv1), K24
         (the two 5x5 convolutions with the block's add and ReLUs).  BatchNorm uses its running statistics whatever .train() says;
-        the extractor is frozen: the features carry no gradient.  `images` is only read."""
+        the extractor is frozen: the features carry no gradient.  `images` is only read.
+        After set_extractor_training(), in .train() mode under enabled gradients, the ResNet front runs exactly as above and the final
+        block runs _final_block_train: batch statistics, gradients into extractor_final_conv.* and through the features.  One
+        deviation from the reference remains there: the frozen front keeps its running statistics in .train(), where the reference's
+        whole model uses batch statistics.  Under torch.no_grad(), or in .eval() without gradients, the switch changes nothing."""
         if not self.has_extractor:
             raise self._no_extractor()
         if not torch.is_tensor(images) or images.dim() != 5 or tuple(images.shape[1:3]) != (2, 3):
             raise ValueError(f'images: (B, 2, 3, H, W), got {tuple(images.shape) if torch.is_tensor(images) else type(images)}')
-        if torch.is_grad_enabled() and any(p.requires_grad for m in (self.resnet, self.extractor_final_conv) for p in m.parameters()):
-            raise NotImplementedError('ViTEss: training the extractor (resnet.* / extractor_final_conv.*) is not built -- its kernels are '
-                                      'inference kernels and its BatchNorm layers use running statistics; keep its parameters at '
-                                      'requires_grad=False (the constructor sets that) or call it under torch.no_grad()')
+        train_final = False
+        if torch.is_grad_enabled():
+            switch = bool(getattr(self, 'extractor_training', False))
+            if any(p.requires_grad for p in self.resnet.parameters()):
+                raise NotImplementedError('ViTEss: training the extractor front (resnet.*) is not built -- K25 / K26 have no backward '
+                                          'kernels and its BatchNorm layers use running statistics; keep its parameters at '
+                                          'requires_grad=False (set_extractor_training() trains extractor_final_conv only) or call it '
+                                          'under torch.no_grad()')
+            wanted = any(p.requires_grad for p in self.extractor_final_conv.parameters())
+            if wanted and not switch:
+                raise NotImplementedError('ViTEss: an extractor_final_conv.* parameter has requires_grad=True but training the extractor '
+                                          'is off: ViTEss.set_extractor_training() turns the HIP backward of the final block on; or keep '
+                                          'the parameters at requires_grad=False / call it under torch.no_grad()')
+            if wanted and not self.extractor_final_conv.training:
+                raise NotImplementedError('ViTEss: gradients into extractor_final_conv.* are wanted (set_extractor_training()) with the '
+                                          'block in .eval() mode: its training kernels use batch statistics -- call .train(), '
+                                          'set_extractor_training(on=False), or run under torch.no_grad()')
+            train_final = wanted
         if not images.is_cuda:
             raise ops._lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
         grid_intrinsics = None if intrinsics is None else update_intrinsics(images.shape, intrinsics)
@@ -416,6 +470,11 @@ class ViTEss(nn.Module):
             for lname, layer in (('layer1', rn.layer1), ('layer2', rn.layer2)):
                 for i, blk in enumerate(layer):
                     x = self._block(pk, f'{lname}.{i}', blk, x)                                          # -> (2B, 28, 28, 128)
+        if train_final:
+            # the final block on the training kernels: its output carries gradients into the trunk (set_extractor_training)
+            x = self._final_block_train(x)
+            return x.reshape(x.shape[0], self.num_patches, DIM), grid_intrinsics
+        with torch.no_grad():
             p1 = pk.get('final.conv1', _fold_tensors(fc.conv1, fc.norm1), lambda: ops.PackedConv(fc.conv1.weight, *_fold(fc.conv1, fc.norm1)))
             p2 = pk.get('final.conv2', _fold_tensors(fc.conv2, fc.norm2), lambda: ops.PackedConvValid(fc.conv2.weight, *_fold(fc.conv2, fc.norm2)))
             pd = pk.get('final.downsample', _fold_tensors(fc.downsample[0], fc.norm3),

@@ -30,7 +30,7 @@ typedef struct ihipStream_t* far_stream_t; /* == hipStream_t */
 
 /* ABI version of this header; bumped when a signature changes (2: activation exponent / overflow flag of K9, K13, K14; 3: the
  * far_wino_* / far_conv3x3_wino_f32 entry points, 16 tuning keys; 4: far_upsample2x_bwd_f32, far_fine_scatter_det_f32, far_bn_train_*, far_adamw_*; 5: far_linear_kv_f16s, far_linear_q_apply_f16s,
- * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way, and so were far_grad_norm_workspace_bytes, far_grad_norm_f32, far_grad_clip_scale_f32 and far_adam_step_f32, and the five far_bn_sync_*_f32 entry points, and the far_conv_valid_* / far_stem_rgb_* / far_maxpool3x3s2_nhwc_f32 entry points of K24-K26).  far_amd/_lib.py refuses a library whose version differs. */
+ * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way, and so were far_grad_norm_workspace_bytes, far_grad_norm_f32, far_grad_clip_scale_f32 and far_adam_step_f32, and the five far_bn_sync_*_f32 entry points, and the far_conv_valid_* / far_stem_rgb_* / far_maxpool3x3s2_nhwc_f32 entry points of K24-K26, and K24's backward: far_conv_valid_pack_dgrad_f32, far_conv_valid_dgrad_f16s, far_conv_valid_wgrad_ws_bytes, far_conv_valid_wgrad_f16s -- pure additions, which tests/test_dense_spvs_cpu.py holds at 8).  far_amd/_lib.py refuses a library whose version differs. */
 int far_abi_version(void);
 /* Id of the sources the library was built from: sha256/16 over far_amd/csrc/* and the compiler flags (far_amd/build.py
  * source_id()).  far_amd/_lib.py refuses a library whose id differs from the sources it sits next to. */
@@ -782,12 +782,29 @@ int far_stem7x7_wgrad_f32(const float* img, const float* dy, int N, int H, int W
  * (torch layout) times pack_scale[0] (far_weight_scale_f32's two device floats) into `packed`, and scale_vec[co] = base_scale[co]
  * (1 when NULL) * pack_scale[1], the vector the launch takes as `scale`.  shift may be NULL; act: 0 none, 1 ReLU (NaN kept);
  * act_exp / overflow as far_conv_nhwc_f32.  Deterministic; image n's output does not depend on N.  y aliases neither x nor res.
+ * Backward (training the extractor's final block; autograd's backward of the same two layers), same shape conditions, -22 otherwise:
+ *   far_conv_valid_dgrad_f16s: dx[n][iy][ix][ci] = sum_{ky,kx,co} dy[n][iy-ky][ix-kx][co] W[co][ci][ky][kx], terms outside dy zero; the
+ *     same tile loop on the image far_conv_valid_pack_dgrad_f32 writes (channels exchanged, taps reversed, packed with the FORWARD
+ *     image's pack_scale), the patch load knows the border: no padded copy of dy.  dy [N][H-4][W-4][Cout] is multiplied by
+ *     dy_scale_dev[0] (far_grad_scale_f32's two device floats, required) before the split; dx [N][H][W][Cin] is overwritten.
+ *     One launch form: image n's dx is the same bits alone or in a batch.
+ *   far_conv_valid_wgrad_f16s: dw[co][ci][ky][kx] = sum_{n,oy,ox} dy[n][oy][ox][co] x[n][oy+ky][ox+kx][ci]; K16's contract: x times
+ *     2^act_exp (the exponent the forward consumed it with, [-24, 15]), dy times dy_scale_dev[0] (NULL: computed by this call), pixel
+ *     ranges write partial sums to `ws` (far_conv_valid_wgrad_ws_bytes() bytes, 0 for a shape not covered), a second kernel adds them
+ *     in a fixed order; overflow: device int OR-ed with 1 on a non-finite sum, or NULL; dw [Cout][Cin][5][5] is overwritten.
+ *   Both: split-fp16 operands, fp32 accumulation, no atomics on floats, run-to-run the same bits.
  * --------------------------------------------------------------------------------------------------- */
 size_t far_conv_valid_packed_bytes(int Cin, int Cout, int ksize);
 int far_conv_valid_pack_f32(const float* w, int Cin, int Cout, int ksize, const float* pack_scale, void* packed, const float* base_scale,
                             float* scale_vec, far_stream_t stream);
 int far_conv_valid_f16s(const float* x, const void* packed, const float* scale, const float* shift, const float* res, float* y, long N,
                         int H, int W, int Cin, int Cout, int ksize, int act, int act_exp, int* overflow, far_stream_t stream);
+int far_conv_valid_pack_dgrad_f32(const float* w, int Cin, int Cout, int ksize, const float* pack_scale, void* packed, far_stream_t stream);
+int far_conv_valid_dgrad_f16s(const float* dy, const void* packed_dgrad, const float* pack_scale, const float* dy_scale_dev, float* dx, long N,
+                              int H, int W, int Cin, int Cout, int ksize, int* overflow, far_stream_t stream);
+long far_conv_valid_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int ksize);
+int far_conv_valid_wgrad_f16s(const float* x, const float* dy, int N, int H, int W, int Cin, int Cout, int ksize, int act_exp,
+                              const float* dy_scale_dev, void* ws, long ws_bytes, float* dw, int* overflow, far_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * K25  RGB stem of the 8-Point-ViT's extractor, one launch; K26  max-pool 3x3 stride 2 pad 1 (NHWC, exact)
