@@ -295,8 +295,13 @@ def uses_lds_dma(src):
 
 
 def uses_split_asm(src):
-    """Files whose kernels form fp16 operand pairs with common.h's asm split (or their own copy): scanned for the half-register hazard."""
+    """Files whose kernels form fp16 operand pairs with common.h's asm split (or their own copy): scanned for the half-register hazard.
+    A call may stand in a recipe header the file includes in quotes (one level; common.h only defines the split, every file includes it)."""
     txt = open(src).read()
+    for h in re.findall(r'^#include "([^"]+)"', txt, re.M):
+        p = os.path.join(os.path.dirname(src), h)
+        if h != 'common.h' and os.path.exists(p):
+            txt += open(p).read()
     return os.path.basename(src) != 'abi.hip' and bool(re.search(r'\bsplit2\(|\bsplit8\(|v_fma_mixhi_f16', txt))
 
 

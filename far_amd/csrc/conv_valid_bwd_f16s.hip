@@ -5,9 +5,10 @@
 // 128 -> 192) of the ResidualBlock model.py:60 builds with kernel_size 5, which train.py fine-tunes with the trunk.
 //
 // dgrad  dx[n][iy][ix][ci] = sum_{ky, kx, co} dy[n][iy - ky][ix - kx][co] w[co][ci][ky][kx]  (terms outside dy are zero): the 'full'
-//   correlation of dy with the flipped, channel-transposed kernel.  K24's tile loop on its own weight image (k_valid_pack_dgrad); the
-//   patch load knows the border: pixel (py, px) of a workgroup's patch is dy[oy0 + py - 4][ox0 + px - 4] or zero, no padded copy of dy
-//   exists.  dy is multiplied by far_grad_scale_f32's device power of two before the split, the epilogue takes it out again.
+//   correlation of dy with the flipped, channel-transposed kernel.  K24's tile loop (conv_valid_tile.inc) and pack kernel
+//   (conv_valid_f16s.h) on the dgrad form of the weight image; the patch load knows the border: pixel (py, px) of a workgroup's patch
+//   is dy[oy0 + py - 4][ox0 + px - 4] or zero, no padded copy of dy exists.  dy is multiplied by far_grad_scale_f32's device power of
+//   two before the split, the epilogue takes it out again.
 //   One form for every launch size: a 16 x 8 tile of dx per workgroup, a wave owns 8 rows x two or three 32-channel N-tiles.  The sum
 //   of an element runs over (chunk, tap, k-step) in that order whatever N is.
 // wgrad  dw[co][ci][ky][kx] = sum_{n, oy, ox} dy[n][oy][ox][co] x[n][oy + ky][ox + kx][ci]: a GEMM whose reduction runs over pixels, so
@@ -15,35 +16,24 @@
 //   and walks 16-pixel-wide column strips downwards: every x row is read from memory once, scaled, split and written TRANSPOSED
 //   ([channel][pixel], 48 B per channel: conflict-free 16-byte reads) into a ring of eight rows in LDS; wave ky reads row oy + ky of the
 //   ring, and the five kx-shifted operands are cut from one 16-pixel fragment in registers.  The (image, strip, row) sequence is cut
-//   into ranges, each range writes its partial dw to a workspace slab, k_valid_wgrad_reduce adds the slabs in index order:
+//   into ranges, each range writes its partial dw to a workspace slab, K16's reduction (wgrad_reduce.h) adds the slabs in index order:
 //   deterministic, no atomics on floats (K16's contract).
-#include "common.h"
+#include "conv_valid_f16s.h"
+#include "wgrad_reduce.h"
 
 extern "C" int far_grad_scale_f32(const float* x, long n, float* out2, hipStream_t stream);
 
 namespace {
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int KS = 5, TAPS = KS * KS;
-
-bool valid_shape(int Cin, int Cout, int ksize) {
-    return ksize == KS && Cin > 0 && Cout > 0 && (Cin & 31) == 0 && (Cout & 31) == 0;
-}
 
 // ------------------------------------------------------------------------------------------------------------------ dgrad
 
-constexpr int TW = 8, PW = TW + KS - 1;                 // tile width of a workgroup; patch width 12
-constexpr int PSTR = 40;                                // fp16 per patch pixel and plane: 32 channels + 8 of padding (K24's layout)
-constexpr int NTHR = 256;
-constexpr int STEPS = TAPS * 2;                         // k-steps of 16 channels per chunk
 constexpr int MTD = 2;                                  // 4 x 8-pixel M-tiles per wave: a 16 x 8 tile of dx per workgroup
 
 struct DgradArgs {
     const float* dy;         // [N][Ho][Wo][Cout]
-    const _Float16* w;       // k_valid_pack_dgrad's image
+    const _Float16* w;       // k_valid_pack<true>'s image
     const float* sg_dev;     // { 2^e, 2^(4 - e) }: dy is multiplied by [0] before the split
     const float* pack_scale; // { 2^w_exp, 2^-(w_exp + 4) } of the image
     float* dx;               // [N][H][W][Cin]
@@ -54,11 +44,7 @@ struct DgradArgs {
 // NTW: 32-channel N-tiles (of Cin) per wave; the workgroup covers 2 NTW of them per blockIdx.y.
 template <int NTW>
 __global__ __launch_bounds__(NTHR) void k_valid_dgrad(const DgradArgs p) {
-    constexpr int MT = MTD, TH = 8 * MT, PH = TH + KS - 1;
-    constexpr int NITEMS = PH * PW * 8;                 // float4 loads per chunk
-    constexpr int ITEMS = (NITEMS + NTHR - 1) / NTHR;
-    __shared__ __attribute__((aligned(16))) _Float16 hi[PH * PW * PSTR];
-    __shared__ __attribute__((aligned(16))) _Float16 lo[PH * PW * PSTR];
+    constexpr int MT = MTD, TH = 8 * MT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l31 = lane & 31, h = lane >> 5;
     const int mh = wave & 1, nh = wave >> 1;
     int t = blockIdx.x;
@@ -67,107 +53,17 @@ __global__ __launch_bounds__(NTHR) void k_valid_dgrad(const DgradArgs p) {
     const int ty = t % p.tilesY, n = t / p.tilesY;
     const int oy0 = ty * TH, ox0 = tx * TW;                        // of dx; the patch starts at dy[oy0 - 4][ox0 - 4]
     const int NT = p.Cin >> 5, nt0 = (blockIdx.y * 2 + nh) * NTW, nchunks = p.Cout >> 5;
-    const float* gin = p.dy + (size_t)n * p.Ho * p.Wo * p.Cout;
-    const float sg = p.sg_dev[0];
-
-    f32x16 acc[MT][NTW], accs[MT][NTW];                            // hi.hi apart from the cross terms, as K24
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][nt][r] = accs[mt][nt][r] = 0.f;
-
-    const bool live = oy0 + 4 * MT * mh < p.H && nt0 < NT;         // wave-uniform
-    const int abase = ((4 * MT * mh + (l31 >> 3)) * PW + (l31 & 7)) * PSTR + 8 * h;
-    const f32x2 sg2 = {sg, sg};
-
-    f16x8 bh[2][NTW], bl[2][NTW];
-    auto fetch = [&](int c, int j, int slot) {
-        const _Float16* wt = p.w + ((size_t)(c * STEPS + j) * NT + nt0) * 1024 + lane * 8;
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt)
-            if (nt0 + nt < NT) {                                   // wave-uniform
-                bh[slot][nt] = *reinterpret_cast<const f16x8*>(wt + nt * 1024);
-                bl[slot][nt] = *reinterpret_cast<const f16x8*>(wt + nt * 1024 + 512);
-            }
-    };
-
-    for (int c = 0; c < nchunks; ++c) {
-        if (live) fetch(c, 0, 0);
-        __syncthreads();                                           // the previous chunk's planes are consumed
-        {
-            float4 v[ITEMS];
-#pragma unroll
-            for (int j = 0; j < ITEMS; ++j) {
-                const int i = tid + NTHR * j, pix = i >> 3, q = i & 7;
-                const int py = pix / PW, px = pix - py * PW;
-                const int gy = oy0 + py - (KS - 1), gx = ox0 + px - (KS - 1);      // the border: outside dy is zero
-                v[j] = (i < NITEMS && gy >= 0 && gy < p.Ho && gx >= 0 && gx < p.Wo)
-                           ? *reinterpret_cast<const float4*>(gin + ((size_t)gy * p.Wo + gx) * p.Cout + 32 * c + 4 * q)
-                           : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-#pragma unroll
-            for (int j = 0; j < ITEMS; ++j) {
-                const int i = tid + NTHR * j, pix = i >> 3, q = i & 7;
-                f16x2 h0, l0, h1, l1;
-                split2(f32x2{v[j].x, v[j].y} * sg2, h0, l0);
-                split2(f32x2{v[j].z, v[j].w} * sg2, h1, l1);
-                if (i < NITEMS) {
-                    *reinterpret_cast<f16x4*>(hi + pix * PSTR + 4 * q) = f16x4{h0.x, h0.y, h1.x, h1.y};
-                    *reinterpret_cast<f16x4*>(lo + pix * PSTR + 4 * q) = f16x4{l0.x, l0.y, l1.x, l1.y};
-                }
-            }
-        }
-        __syncthreads();
-        if (!live) continue;
-        auto step = [&](int off, int cur) {
-            f16x8 ah[MT], al[MT];
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) {
-                ah[mt] = *reinterpret_cast<const f16x8*>(hi + off + 4 * mt * PW * PSTR);
-                al[mt] = *reinterpret_cast<const f16x8*>(lo + off + 4 * mt * PW * PSTR);
-            }
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt) {
-                if (nt0 + nt < NT) {
-#pragma unroll
-                    for (int mt = 0; mt < MT; ++mt) {
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bh[cur][nt], acc[mt][nt], 0, 0, 0);
-                        accs[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bl[cur][nt], accs[mt][nt], 0, 0, 0);
-                        accs[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mt], bh[cur][nt], accs[mt][nt], 0, 0, 0);
-                    }
-                }
-            }
-        };
-#pragma unroll 1
-        for (int dy = 0; dy < KS; ++dy) {
-#pragma unroll 1
-            for (int dx = 0; dx < KS; ++dx) {
-                const int tap = dy * KS + dx, off = abase + (dy * PW + dx) * PSTR;
-                fetch(c, 2 * tap + 1, 1);
-                step(off, 0);
-                if (tap + 1 < TAPS) fetch(c, 2 * tap + 2, 0);
-                step(off + 16, 1);
-            }
-        }
-    }
-    if (!live) return;
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int nt = 0; nt < NTW; ++nt) acc[mt][nt] += accs[mt][nt];
-
-    if (p.overflow) {                                              // a non-finite dy reaches the accumulators: as K24's guard
-        float chk = 0.f;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) chk += acc[mt][nt][r];
-        if (__any(!(fabsf(chk) <= FLT_MAX)) && lane == 0) atomicOr(p.overflow, 1);
-    }
+    // The fragment's names.  The references exist only to steer code generation: each field is then read where the loop uses it, as
+    // when the loop stood here, and the kernel compiles to the same instructions as then.  Plain copies, or another order of these
+    // lines, change the generated code (conv_valid_tile.inc).
+    constexpr int PAD = KS - 1;
+    const float* const src = p.dy + (size_t)n * p.Ho * p.Wo * p.Cout;
+    const int &src_rows = p.Ho, &src_cols = p.Wo, &src_C = p.Cout;
+    const float src_scale = p.sg_dev[0];
+    const _Float16* const& wimg = p.w;
+    int* const& overflow = p.overflow;
+    const int& out_rows = p.H;
+#include "conv_valid_tile.inc"
 
     const float inv_g = p.sg_dev[1] * 0.0625f, inv_w = p.pack_scale[1] * 16.0f;    // 2^-e and 2^-w_exp
 #pragma unroll
@@ -183,38 +79,6 @@ __global__ __launch_bounds__(NTHR) void k_valid_dgrad(const DgradArgs p) {
                 if (iy < p.H && ix < p.W) p.dx[(((size_t)n * p.H + iy) * p.W + ix) * p.Cin + ci] = acc[mt][nt][r] * inv_w * inv_g;
             }
         }
-    }
-}
-
-// The dgrad image: K24's layout with the channels exchanged and the taps reversed.  Item (chunk c, tap t, k-step s, N-tile nt, lane):
-// the eight OUTPUT channels co = 32 c + 16 s + 8 (lane >> 5) + e of the forward layer (the reduction of the dgrad) for its input channel
-// ci = 32 nt + (lane & 31) at tap 24 - t, times pack_scale[0] (the forward image's scale: the same maximum).
-__global__ __launch_bounds__(256) void k_valid_pack_dgrad(const float* __restrict__ w, int Cin, int Cout, const float* __restrict__ pack_scale,
-                                                          _Float16* __restrict__ packed) {
-    const int NT = Cin >> 5;
-    const long items = (long)(Cout >> 5) * TAPS * 2 * NT * 64;
-    const float wmul = pack_scale[0];
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long)gridDim.x * 256) {
-        const int ln = (int)(i & 63);
-        long u = i >> 6;
-        const int nt = (int)(u % NT);
-        u /= NT;
-        const int s = (int)(u & 1);
-        u >>= 1;
-        const int t = (int)(u % TAPS), c = (int)(u / TAPS);
-        const int ci = 32 * nt + (ln & 31);
-        f16x8 vh, vl;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const int co = 32 * c + 16 * s + 8 * (ln >> 5) + e;
-            const float v = w[((size_t)co * Cin + ci) * TAPS + (TAPS - 1 - t)] * wmul;
-            const _Float16 hh = (_Float16)v;
-            vh[e] = hh;
-            vl[e] = (_Float16)(v - (float)hh);
-        }
-        _Float16* dst = packed + (size_t)(i >> 6) * 1024 + ln * 8;
-        *reinterpret_cast<f16x8*>(dst) = vh;
-        *reinterpret_cast<f16x8*>(dst + 512) = vl;
     }
 }
 
@@ -359,22 +223,6 @@ __global__ __launch_bounds__(WTHR) void k_valid_wgrad(const WgArgs p) {
             }
 }
 
-// dw[co][ci][t] = (sum over slabs of part[slab][t][co][ci]) / (sx sg), slabs in index order; overflow |= a non-finite sum.
-__global__ void k_valid_wgrad_reduce(const float* __restrict__ part, int slabs, long cc, const float* __restrict__ sg_dev, float inv_sx,
-                                     float* __restrict__ dw, int* __restrict__ overflow) {
-    const long total = cc * TAPS;
-    const float inv = inv_sx / sg_dev[0];
-    bool bad = false;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        float s = 0.f;
-        for (int k = 0; k < slabs; ++k) s += part[(size_t)k * total + i];
-        const long t = i / cc, e = i - t * cc;
-        bad |= !(fabsf(s) <= FLT_MAX);
-        dw[e * TAPS + t] = s * inv;
-    }
-    if (overflow && bad) atomicOr(overflow, 1);
-}
-
 struct WgPlan {
     int strips, cpairs, tiles;
     long units, units_per_range, slabs;
@@ -406,10 +254,7 @@ extern "C" {
 int far_conv_valid_pack_dgrad_f32(const float* w, int Cin, int Cout, int ksize, const float* pack_scale, void* packed, hipStream_t stream) {
     far_clear_errors();
     if (!w || !pack_scale || !packed || !valid_shape(Cin, Cout, ksize)) return FAR_EINVAL;
-    const long items = (long)(Cout >> 5) * TAPS * 2 * (Cin >> 5) * 64;
-    long blocks = (items + 255) / 256;
-    blocks = blocks > 1024 ? 1024 : blocks;
-    hipLaunchKernelGGL(k_valid_pack_dgrad, dim3((unsigned)blocks), dim3(256), 0, stream, w, Cin, Cout, pack_scale, (_Float16*)packed);
+    valid_pack<true>(w, Cin, Cout, pack_scale, packed, nullptr, nullptr, stream);
     return far_check_launch();
 }
 
@@ -468,9 +313,7 @@ int far_conv_valid_wgrad_f16s(const float* x, const float* dy, int N, int H, int
     a.sx = ldexpf(1.0f, act_exp);
     if (pl.slabs > 65535) return FAR_EINVAL;
     hipLaunchKernelGGL(k_valid_wgrad, dim3((unsigned)pl.tiles, (unsigned)pl.slabs), dim3(WTHR), 0, stream, a);
-    const long cc = (long)Cout * Cin, total = cc * TAPS;
-    hipLaunchKernelGGL(k_valid_wgrad_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a.part, (int)pl.slabs, cc, dy_scale_dev,
-                       ldexpf(1.0f, -act_exp), dw, overflow);
+    wgrad_reduce(a.part, pl.slabs, TAPS, (long)Cout * Cin, dy_scale_dev, ldexpf(1.0f, -act_exp), dw, overflow, stream);
     return far_check_launch();
 }
 

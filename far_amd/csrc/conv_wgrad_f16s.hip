@@ -22,6 +22,7 @@
 // through L1); each range writes its partial dW to a workspace slab and k_wgrad_reduce sums the slabs in a fixed order:
 // deterministic, no atomics.
 #include "common.h"
+#include "wgrad_reduce.h"
 
 extern "C" int far_grad_scale_f32(const float* x, long n, float* out2, hipStream_t stream);
 
@@ -263,22 +264,6 @@ __global__ __launch_bounds__(256, (KS == 3 && ST == 2) ? 1 : 2) void k_wgrad_s(c
     }
 }
 
-// dw[co][ci][t] = (sum over slabs of part[slab][t][co][ci]) / (sx sg), slabs in index order; overflow |= a non-finite sum.
-__global__ void k_wgrad_reduce(const float* __restrict__ part, int slabs, int taps, long cc, const float* __restrict__ sg_dev, float inv_sx,
-                               float* __restrict__ dw, int* __restrict__ overflow) {
-    const long total = cc * taps;
-    const float inv = inv_sx / sg_dev[0];
-    bool bad = false;
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        float s = 0.f;
-        for (int k = 0; k < slabs; ++k) s += part[(size_t)k * total + i];
-        const long t = i / cc, e = i - t * cc;
-        bad |= !(fabsf(s) <= FLT_MAX);
-        dw[e * taps + t] = s * inv;
-    }
-    if (overflow && bad) atomicOr(overflow, 1);
-}
-
 struct Plan {
     int strips, wgs_per_range;
     long units, units_per_range, slabs;
@@ -366,11 +351,7 @@ int far_conv_wgrad_f16s(const float* x, const float* dy, int N, int H, int W, in
     } else {
         if (stride == 1) launch_ws<1, 1>(a, pl, stream); else launch_ws<1, 2>(a, pl, stream);
     }
-    const long cc = (long)Cout * Cin;
-    const int taps = ksize * ksize;
-    const long total = cc * taps;
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, a.part, (int)pl.slabs, taps, cc,
-                       dy_scale_dev, ldexpf(1.0f, -act_exp), dw, overflow);
+    wgrad_reduce(a.part, pl.slabs, ksize * ksize, (long)Cout * Cin, dy_scale_dev, ldexpf(1.0f, -act_exp), dw, overflow, stream);
     return far_check_launch();
 }
 

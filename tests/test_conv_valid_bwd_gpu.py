@@ -5,7 +5,8 @@ Inputs are signed, from seeded device generators; gradients dy ~ 1e-3 randn (as 
 project's parity rule (tests/test_full_attention_gpu.py: _bar) -- at most max(3 x dev32, 2^-20 max|r64|) from float64 torch autograd of
 F.conv2d, with dev32 the deviation of fp32 torch autograd on the same GPU in the same run.  Shapes: 5 x 5 (one output pixel: every input
 pixel receives one tap, dw is the plain outer product), 9 x 11 (partial tiles in both directions, 35 output pixels), 28 x 28 (the
-workload), channels 32 / 128 / 192 -> 192 (dgrad's output channel count is Cin: 32 and 128 leave N-tiles of its workgroups empty)."""
+workload), channels 32 / 128 / 192 -> 192 (dgrad's output channel count is Cin: 32 and 128 leave N-tiles of its workgroups empty),
+and 32 -> 32, 64 -> 160 at 9 x 11 (the only cases whose Cout is not six full N-tiles)."""
 import functools
 
 import pytest
@@ -29,12 +30,12 @@ def _autograd(x, w, dy, dtype):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(N, H, W, cin):
+def _case(N, H, W, cin, cout=COUT):
     """Inputs and both references of one shape, computed once and shared by the tests (never modified)."""
-    g = _gen(100000 * N + 1000 * H + cin)
+    g = _gen(100000 * N + 1000 * H + cin + (0 if cout == COUT else 7 * cout))
     x = torch.randn(N, H, W, cin, device='cuda', generator=g) * 3
-    w = torch.randn(COUT, cin, 5, 5, device='cuda', generator=g) * (2.0 / (25 * cin)) ** 0.5
-    dy = 1e-3 * torch.randn(N, H - 4, W - 4, COUT, device='cuda', generator=g)
+    w = torch.randn(cout, cin, 5, 5, device='cuda', generator=g) * (2.0 / (25 * cin)) ** 0.5
+    dy = 1e-3 * torch.randn(N, H - 4, W - 4, cout, device='cuda', generator=g)
     dx64, dw64 = _autograd(x, w, dy, torch.float64)
     dx32, dw32 = _autograd(x, w, dy, torch.float32)
     return x, w, dy, dx64, dw64, float((dx32.double() - dx64).abs().max()), float((dw32.double() - dw64).abs().max())
@@ -88,6 +89,29 @@ def test_conv_valid_wgrad_against_float64(nhw, cin):
     _bar(f'conv_valid_wgrad {cin}->192 @ {N}x{H}x{W}', got, dw64, dev32)
     assert not ops.activation_overflowed('cuda')
     assert torch.equal(ops.conv_valid_wgrad(x, dy, dy_scale=ops.grad_scale(dy), act_exp=4), got)
+
+
+@pytest.mark.parametrize('cin,cout', [(32, 32), (64, 160)])
+def test_partial_n_tiles_against_float64(cin, cout):
+    """Cout = 32 and 160 (every other case has 192): the dgrad reduces over one and five chunks instead of six; the wgrad's last pair of
+    co tiles has one tile only; Cin = 32 / 64 leave N-tiles of the dgrad's workgroups empty."""
+    from far_amd import ops
+    N, H, W = 3, 9, 11
+    x, w, dy, dx64, dw64, dev32x, dev32w = _case(N, H, W, cin, cout)
+    ops.overflow_flag('cuda').zero_()
+    dx = ops.conv_valid_dgrad(dy, w)
+    assert dx.shape == (N, H, W, cin)
+    _bar(f'conv_valid_dgrad {cin}->{cout} @ {N}x{H}x{W}', dx, dx64, dev32x)
+    dw = ops.conv_valid_wgrad(x, dy)
+    assert dw.shape == (cout, cin, 5, 5)
+    _bar(f'conv_valid_wgrad {cin}->{cout} @ {N}x{H}x{W}', dw, dw64, dev32w)
+    assert not ops.activation_overflowed('cuda')
+    # image n's dx does not depend on the batch it is in (under the batch's gradient scale, as above)
+    pd = ops.PackedConvValid(w, dgrad=True, pack_scale=ops.PackedConvValid(w).pack_scale)
+    sc = ops.grad_scale(dy)
+    assert torch.equal(ops.conv_valid_dgrad(dy, pd, dy_scale=sc), dx)
+    assert torch.equal(ops.conv_valid_dgrad(dy[1:2].contiguous(), pd, dy_scale=sc), dx[1:2])
+    assert torch.equal(ops.conv_valid_wgrad(x, dy, dy_scale=sc, act_exp=4), dw)
 
 
 @pytest.mark.parametrize('which', ['dgrad', 'wgrad'])

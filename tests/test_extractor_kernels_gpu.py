@@ -35,14 +35,10 @@ def _conv_ref(x, w, bias, scale, shift, res, relu, dtype, stride=1, padding=0):
     return torch.relu(y) if relu else y
 
 
-@pytest.mark.parametrize('cin', [32, 128, 192])
-@pytest.mark.parametrize('hw', [(9, 11), (5, 5), (28, 28)])
-def test_conv_valid_against_float64(hw, cin):
-    """9 x 11 -> 5 x 7 (partial tiles in both directions), 5 x 5 -> 1 x 1, 28 x 28 -> 24 x 24 (the workload); bare, and with bias + BN
-    fold + residual + ReLU."""
+def _check_conv_valid(hw, cin, cout, seed):
     from far_amd import ops
-    (H, W), N, cout = hw, 3, 192
-    g = _gen(1000 * H + cin)
+    (H, W), N = hw, 3
+    g = _gen(seed)
     x = torch.randn(N, H, W, cin, device='cuda', generator=g) * 3
     w = torch.randn(cout, cin, 5, 5, device='cuda', generator=g) * (2.0 / (25 * cin)) ** 0.5
     bias = 0.2 * torch.randn(cout, device='cuda', generator=g)
@@ -53,16 +49,30 @@ def test_conv_valid_against_float64(hw, cin):
     assert got.shape == (N, H - 4, W - 4, cout)
     r64 = _conv_ref(x, w, None, None, None, None, False, torch.float64)
     r32 = _conv_ref(x, w, None, None, None, None, False, torch.float32)
-    _bar(f'conv_valid {cin}->192 @ {H}x{W} bare', got, r64, float((r32.double() - r64).abs().max()))
+    _bar(f'conv_valid {cin}->{cout} @ {H}x{W} bare', got, r64, float((r32.double() - r64).abs().max()))
     pack = ops.PackedConvValid(w, scale, shift + scale * bias)
     got = ops.conv_valid(x, pack, residual=res, act='relu')
     r64 = _conv_ref(x, w, bias, scale, shift, res, True, torch.float64)
     r32 = _conv_ref(x, w, bias, scale, shift, res, True, torch.float32)
-    _bar(f'conv_valid {cin}->192 @ {H}x{W} bias + BN + residual + ReLU', got, r64, float((r32.double() - r64).abs().max()))
+    _bar(f'conv_valid {cin}->{cout} @ {H}x{W} bias + BN + residual + ReLU', got, r64, float((r32.double() - r64).abs().max()))
     assert 0.2 < float((got > 0).float().mean()) < 0.8                      # the ReLU cuts
     assert not ops.activation_overflowed('cuda')
     # image n's output does not depend on the batch it is in
     assert torch.equal(ops.conv_valid(x[1:2].contiguous(), pack, residual=res[1:2].contiguous(), act='relu'), got[1:2])
+
+
+@pytest.mark.parametrize('cin', [32, 128, 192])
+@pytest.mark.parametrize('hw', [(9, 11), (5, 5), (28, 28)])
+def test_conv_valid_against_float64(hw, cin):
+    """9 x 11 -> 5 x 7 (partial tiles in both directions), 5 x 5 -> 1 x 1, 28 x 28 -> 24 x 24 (the workload); bare, and with bias + BN
+    fold + residual + ReLU."""
+    _check_conv_valid(hw, cin, 192, 1000 * hw[0] + cin)
+
+
+@pytest.mark.parametrize('cin,cout', [(32, 32), (64, 160)])
+def test_conv_valid_partial_n_tiles_against_float64(cin, cout):
+    """Cout = 32 and 160 are no six full N-tiles (every other case has 192): a wave without an N-tile, waves with one or two of three."""
+    _check_conv_valid((9, 11), cin, cout, 9000 + cin + 7 * cout)
 
 
 def test_conv_valid_small_and_large_launches_have_the_same_bits():

@@ -316,6 +316,31 @@ def test_build_scan_flags_a_half_register_write_read_too_soon(tmp_path):
         assert len(bad) == nbad and n == (0 if name == 'not from asm' else 1), (name, n, bad)
 
 
+def test_build_half_register_scan_sees_a_split_in_an_included_header(tmp_path):
+    """far_amd/build.py: uses_split_asm decides which files are compiled to assembly for partial_write_check.  A file whose split2( calls
+    stand in a file it includes in quotes is scanned like one that calls it itself -- conv_valid_f16s.hip holds no split2( of its own, the
+    calls of K24's tile loop are in conv_valid_tile.inc, which it includes directly; the scan looks ONE level deep, so that include must
+    stay in the .hip file (through conv_valid_f16s.h it would be two levels, and the assertions on the tree's files here would fail).  Including common.h,
+    which only defines the split, is no use of it."""
+    from far_amd import build
+    (tmp_path / 'common.h').write_text('__device__ void split2(f32x2 v, f16x2& hi, f16x2& lo) { asm volatile("v_fma_mixhi_f16 ..."); }\n')
+    (tmp_path / 'recipe.h').write_text('#pragma once\n#include "common.h"\n__device__ void tile() { split2(v, h, l); }\n')
+    (tmp_path / 'plain.h').write_text('#pragma once\n#include "common.h"\n__device__ void tile() {}\n')
+    cases = {'direct.hip': ('#include "common.h"\n__global__ void k() { split2(v, h, l); }\n', True),
+             'through_header.hip': ('// a kernel\n#include "recipe.h"\n__global__ void k() { tile(); }\n', True),
+             'no_split.hip': ('#include "common.h"\n#include "plain.h"\n#include <cmath>\n#include "not_there.h"\n__global__ void k() { tile(); }\n', False)}
+    for name, (text, want) in cases.items():
+        (tmp_path / name).write_text(text)
+        assert build.uses_split_asm(str(tmp_path / name)) is want, name
+    (tmp_path / 'outer.h').write_text('#pragma once\n#include "recipe.h"\n')
+    (tmp_path / 'two_levels.hip').write_text('#include "outer.h"\n__global__ void k() { tile(); }\n')
+    assert build.uses_split_asm(str(tmp_path / 'two_levels.hip')) is False                # documented: one level only
+    for name in ('conv_valid_f16s.hip', 'conv_valid_bwd_f16s.hip', 'conv_wgrad_f16s.hip'):
+        assert build.uses_split_asm(os.path.join(build.CSRC, name)), name
+    assert 'split2(' not in open(os.path.join(build.CSRC, 'conv_valid_f16s.hip')).read()       # in the scan only through the fragment
+    assert not build.uses_split_asm(os.path.join(build.CSRC, 'layernorm_f32.hip'))
+
+
 def test_build_ring_scan_flags_a_barrier_crossed_with_lds_reads_outstanding(tmp_path):
     """far_amd/build.py: lds_ring_check -- the build gate behind the round-6 root cause (common.h: ring_barrier).  On hand-made code:
     the rounds-3..5 shape of K13 / K14 (two fragment reads, vmcnt wait, barrier, THEN the lgkmcnt wait hipcc sank below it) is flagged;

@@ -5,7 +5,8 @@ The float64 yardstick of tests/test_vit8pt_extractor_train_gpu.py runs tests/vit
 autograd, on the seeded case of tests/vit8pt_extractor_train_ref.py) pins that to the reference at 1e-5 relative, the README's parity
 line for float64-against-reference vectors: max|restatement - fixture| <= 1e-5 max|fixture| per tensor.  The three convolution bias
 gradients are mathematically zero under batch statistics (the fixture holds the reference's fp32 rounding noise): they are held to
-1e-5 of the largest gradient of the BatchNorm bias behind them.  The switch itself (ViTEss.set_extractor_training) needs no GPU either."""
+1e-5 of the largest gradient of the BatchNorm bias behind them.  The switch itself (ViTEss.set_extractor_training) needs no GPU either,
+nor do the sizes K24 asks its callers for."""
 import os
 
 import numpy as np
@@ -70,3 +71,20 @@ def test_the_setter_and_the_refusals():
         m.extract_features(images)
     with pytest.raises(NotImplementedError, match='forward_features'):            # a model without the extractor: as forward(images)
         ViTEss(vi.vit_args()).set_extractor_training()
+
+
+def test_k24_image_and_wgrad_workspace_sizes_are_pinned():
+    """The packed image is 25 taps x Cin x Cout x (hi + lo) fp16 in either direction; the weight gradient's workspace is 256 bytes (the
+    gradient scale) + one fp32 slab [25][Cout][Cin] per pixel range of its plan.  Literals, as the library gave them before the forward
+    and the dgrad came to share conv_valid_f16s.h: the slab plan must not drift."""
+    from far_amd import _lib
+    lib = _lib.load()
+    pinned = {(1, 5, 5, 32, 32): (102656, 102400), (3, 9, 11, 32, 192): (614656, 614400), (3, 28, 28, 128, 192): (44237056, 2457600),
+              (64, 28, 28, 128, 192): (103219456, 2457600), (64, 28, 28, 192, 192): (103219456, 3686400),
+              (2, 28, 28, 64, 160): (12288256, 1024000)}
+    for (N, H, W, cin, cout), (ws, image) in pinned.items():
+        assert lib.far_conv_valid_wgrad_ws_bytes(N, H, W, cin, cout, 5) == ws, (N, H, W, cin, cout)
+        assert lib.far_conv_valid_packed_bytes(cin, cout, 5) == image == 100 * cin * cout, (cin, cout)
+    for refused in ((3, 9, 11, 32, 192, 3), (3, 9, 11, 48, 192, 5), (0, 9, 11, 32, 192, 5), (3, 4, 11, 32, 192, 5)):      # ksize 3, Cin 48, N = 0, H = 4
+        assert lib.far_conv_valid_wgrad_ws_bytes(*refused) == 0, refused
+    assert lib.far_conv_valid_packed_bytes(32, 192, 3) == 0 and lib.far_conv_valid_packed_bytes(48, 192, 5) == 0

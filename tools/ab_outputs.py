@@ -1,8 +1,10 @@
-"""Same-box A/B of output BITS: runs K22 (ops.full_attention_train), K23 (ops.vit_attention_train, vit_attention_train_qkv) and the
-K1 training ops (ops.coarse_pos_conf, coarse_dense_focal_loss, sinkhorn_pos_conf, sinkhorn_dense_focal_loss) forward and backward
-on seeded inputs with far_amd/lib/libfar_hip_base.so (tools/ab_build.py) and with the working tree's library, each in a fresh child
-process, and compares the sha256 of every output (out, lse, dq, dk, dv; values, loss, df0, df1, dbin).  The kernels are deterministic
-and built with -ffp-contract=off: a refactor that keeps every expression gives equal digests; a difference names the case and the tensor.
+"""Same-box A/B of output BITS: runs K22 (ops.full_attention_train), K23 (ops.vit_attention_train, vit_attention_train_qkv), the
+K1 training ops (ops.coarse_pos_conf, coarse_dense_focal_loss, sinkhorn_pos_conf, sinkhorn_dense_focal_loss) and K24 (ops.conv_valid,
+conv_valid_dgrad, conv_valid_wgrad, conv_valid_train; with two calls of K16's ops.conv_wgrad, whose slab reduction K24 shares) forward
+and backward on seeded inputs with far_amd/lib/libfar_hip_base.so (tools/ab_build.py) and with the working tree's library, each in a
+fresh child process, and compares the sha256 of every output (out, lse, dq, dk, dv; values, loss, df0, df1, dbin; y, dx, dw).  The
+kernels are deterministic and built with -ffp-contract=off: a refactor that keeps every expression gives equal digests; a difference
+names the case and the tensor.
 Usage: python tools/ab_build.py [rev] && python tools/ab_outputs.py      (exit status 1 on any difference or a failed child)"""
 import hashlib
 import json
@@ -84,6 +86,42 @@ def k1_training(np, torch, ops, emit):
                          (loss.detach(),) + torch.autograd.grad(loss, (x0, x1, a), up()))
 
 
+# K24 (Cin, Cout) x (N, H, W): 192 output channels are six full N-tiles, 32 and 160 are not; Cin = 128 takes the dgrad's two-tile form;
+# 3 images take the forward's 8-row launch form, 64 its 24-row form; 9 x 11 has partial tiles in both directions, 5 x 5 one output pixel
+K24_CH = [(32, 192), (128, 192), (192, 192), (32, 32), (64, 160)]
+K24_NHW = [(3, 9, 11), (3, 5, 5), (3, 28, 28), (64, 28, 28)]
+K16 = [(2, 20, 24, 64, 128, 3, 1), (2, 20, 24, 64, 128, 3, 2)]      # (N, H, W, Cin, Cout, ksize, stride): the shared slab reduction
+K24_TRAIN = (2, 9, 11, 128, 192)
+
+
+def k24(np, torch, ops, emit):
+    for i, (cin, cout) in enumerate(K24_CH):
+        for j, (N, H, W) in enumerate(K24_NHW):
+            rng = np.random.default_rng(700 + 10 * i + j)
+            t = lambda *shape, mul=1.0: torch.from_numpy((mul * rng.standard_normal(shape)).astype(np.float32)).cuda()
+            x, w = t(N, H, W, cin, mul=3.0), t(cout, cin, 5, 5, mul=(2.0 / (25 * cin)) ** 0.5)
+            scale, shift, res = 0.5 + t(cout).abs(), t(cout, mul=0.3), t(N, H - 4, W - 4, cout)
+            dy = t(N, H - 4, W - 4, cout, mul=1e-3)
+            tag = f'K24 {cin}->{cout} @ {(N, H, W)}'
+            emit(tag + ' forward', ('y', 'y_fused'), (ops.conv_valid(x, ops.PackedConvValid(w)),
+                                                      ops.conv_valid(x, ops.PackedConvValid(w, scale, shift), residual=res, act='relu')))
+            pd = ops.PackedConvValid(w, dgrad=True, pack_scale=ops.PackedConvValid(w).pack_scale)
+            sc = ops.grad_scale(dy)
+            emit(tag + ' backward', ('dx', 'dw'), (ops.conv_valid_dgrad(dy, pd, dy_scale=sc), ops.conv_valid_wgrad(x, dy, dy_scale=sc)))
+    for i, (N, H, W, cin, cout, ks, st) in enumerate(K16):
+        rng = np.random.default_rng(800 + i)
+        x = torch.from_numpy(rng.standard_normal((N, H, W, cin)).astype(np.float32)).cuda()
+        dy = torch.from_numpy((1e-3 * rng.standard_normal((N, (H - 1) // st + 1, (W - 1) // st + 1, cout))).astype(np.float32)).cuda()
+        emit(f'K16 {cin}->{cout} {ks}x{ks} stride {st} @ {(N, H, W)}', ('dw',), (ops.conv_wgrad(x, dy, ks, st),))
+    N, H, W, cin, cout = K24_TRAIN
+    rng = np.random.default_rng(900)
+    x = torch.from_numpy((3.0 * rng.standard_normal((N, H, W, cin))).astype(np.float32)).cuda().requires_grad_()
+    w = torch.from_numpy((0.03 * rng.standard_normal((cout, cin, 5, 5))).astype(np.float32)).cuda().requires_grad_()
+    dy = torch.from_numpy((1e-3 * rng.standard_normal((N, H - 4, W - 4, cout))).astype(np.float32)).cuda()
+    y = ops.conv_valid_train(x, w, ops.PackCache(), 'layer')
+    emit(f'K24 train {cin}->{cout} @ {(N, H, W)}', ('y', 'dx', 'dw'), (y.detach(),) + torch.autograd.grad(y, (x, w), dy))
+
+
 def child():
     import numpy as np
     import torch
@@ -126,6 +164,7 @@ def child():
     dqkv, = torch.autograd.grad(out, (qkv,), g)
     emit(f'K23 packed {(Z, N, N, H)}', names, (out.detach(), lse) + tuple(dqkv[..., j * H * 64:(j + 1) * H * 64] for j in range(3)))
     k1_training(np, torch, ops, emit)
+    k24(np, torch, ops, emit)
     if ops.activation_overflowed('cuda'):
         sys.exit('the overflow flag is set: the inputs left the split range')
 
