@@ -74,6 +74,7 @@ SIGNATURES = {
     'far_full_attention_bwd_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     'far_full_attention_bwd_f16s': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p]),
     'far_vit_attention_f16s': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_l, c_l, c_l, c_i, c_p, c_p, c_p]),
+    'far_vit_attention_f16': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_l, c_l, c_l, c_i, c_p, c_p, c_p]),   # K23, plain fp16
     'far_vit_attention_train_f16s': (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_l, c_l, c_l, c_l, c_l, c_l, c_i, c_p, c_p, c_p, c_p]),
     'far_vit_attention_bwd_workspace_bytes': (c_sz, [c_i, c_i, c_i, c_i, c_i]),
     'far_vit_attention_bwd_f16s': (c_i, [c_p] * 6 + [c_i] * 5 + [c_l] * 6 + [c_i, c_p, c_p, c_p] + [c_l] * 6 + [c_p, c_p, c_p]),
@@ -151,6 +152,9 @@ SIGNATURES = {
     'far_conv_valid_packed_bytes': (c_sz, [c_i, c_i, c_i]),
     'far_conv_valid_pack_f32': (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
     'far_conv_valid_f16s': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),     # K24
+    'far_conv_valid_f16_packed_bytes': (c_sz, [c_i, c_i, c_i]),
+    'far_conv_valid_pack_f16': (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p]),
+    'far_conv_valid_f16': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),      # K24, plain fp16
     'far_conv_valid_pack_dgrad_f32': (c_i, [c_p, c_i, c_i, c_i, c_p, c_p, c_p]),
     'far_conv_valid_dgrad_f16s': (c_i, [c_p, c_p, c_p, c_p, c_p, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p]),                  # K24 backward
     'far_conv_valid_wgrad_ws_bytes': (c_l, [c_i, c_i, c_i, c_i, c_i, c_i]),

@@ -284,6 +284,8 @@ class LocalFeatureTransformer(nn.Module):
 
 
 class Mlp(nn.Module):
+    split_operands = True        # K9 operand precision of the two Linear layers at inference (False: plain fp16, ViTEss.set_precision)
+
     def __init__(self, in_features, hidden_features=None, out_features=None, act_layer=nn.GELU, drop=0.):
         super().__init__()
         self.fc1 = nn.Linear(in_features, hidden_features or in_features)
@@ -299,8 +301,9 @@ class Mlp(nn.Module):
             y = self.fc2(self.act(self.fc1(x)))
             return y if residual is None else residual + y
         pk = self.__dict__.setdefault('_packs', ops.PackCache())
-        p1 = pk.get('fc1', [self.fc1.weight, self.fc1.bias], lambda: ops.PackedConv(self.fc1.weight, None, self.fc1.bias))
-        p2 = pk.get('fc2', [self.fc2.weight, self.fc2.bias], lambda: ops.PackedConv(self.fc2.weight, None, self.fc2.bias))
+        sp = self.split_operands
+        p1 = pk.get(('fc1', sp), [self.fc1.weight, self.fc1.bias], lambda: ops.PackedConv(self.fc1.weight, None, self.fc1.bias, split=sp))
+        p2 = pk.get(('fc2', sp), [self.fc2.weight, self.fc2.bias], lambda: ops.PackedConv(self.fc2.weight, None, self.fc2.bias, split=sp))
         hid = self.act(ops.linear_f16s(x.contiguous(), p1))
         return ops.linear_f16s(hid, p2, residual=None if residual is None else residual.contiguous())
 

@@ -134,48 +134,51 @@ def full_attention_train(q, k, v, nhead, q_mask=None, kv_mask=None):
     _, _, _, _, _, q_mask, kv_mask = _full_attention_args(q, k, v, nhead, q_mask, kv_mask)
     return _FullAttentionFn.apply(q, k, v, nhead, q_mask, kv_mask)
 
-def _vit_attention_launch(q, k, v, Z, L, S, nhead, q_strides, kv_strides):
-    """far_vit_attention_f16s on operands whose layout the caller has established (strides in floats: image, head, row)."""
+def _vit_attention_launch(q, k, v, Z, L, S, nhead, q_strides, kv_strides, plain16=False):
+    """far_vit_attention_f16s (plain16: far_vit_attention_f16) on operands whose layout the caller has established (strides in
+    floats: image, head, row)."""
     lib = _lib.load()
     _on_gpu(q, k, v)
     _fp32(q, k, v)
+    entry = 'far_vit_attention_f16' if plain16 else 'far_vit_attention_f16s'
     if torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)):
-        raise NotImplementedError('vit_attention (K23, far_vit_attention_f16s) is the inference front end: run it under torch.no_grad() '
+        raise NotImplementedError(f'vit_attention (K23, {entry}) is the inference front end: run it under torch.no_grad() '
                                   'or on tensors that need no gradient; ops.vit_attention_train / vit_attention_train_qkv are the '
-                                  'forms with the HIP backward')
+                                  'forms with the HIP backward' + (' (split-fp16 operands only)' if plain16 else ''))
     out = torch.empty(Z, L, nhead * 64, dtype=torch.float32, device=q.device)
     if Z == 0 or L == 0:
         return out
     if S == 0:
         return out.zero_()
-    rc = lib.far_vit_attention_f16s(ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.data_ptr()), Z, L, S,
-                                    nhead, 64, *q_strides, *kv_strides, activation_exponent_value(), _p(out),
-                                    _p(overflow_flag(q.device)), _stream())
-    _lib.check(rc, 'far_vit_attention_f16s')
+    rc = getattr(lib, entry)(ctypes.c_void_p(q.data_ptr()), ctypes.c_void_p(k.data_ptr()), ctypes.c_void_p(v.data_ptr()), Z, L, S,
+                             nhead, 64, *q_strides, *kv_strides, activation_exponent_value(), _p(out),
+                             _p(overflow_flag(q.device)), _stream())
+    _lib.check(rc, entry)
     return out
 
-def vit_attention(q, k, v, nhead):
+def vit_attention(q, k, v, nhead, plain16=False):
     """K23: the softmax self-attention core of the 8-Point-ViT's Blocks, head dim 64 only, no masks, inference only.  q: (Z, L, C),
     k, v: (Z, S, C) fp32 GPU tensors with the heads concatenated (C = nhead * 64; any other head dim raises FarHipError);
     returns (Z, L, C) = softmax_s(q . k / 8) v per head, on split-fp16 MFMAs with an online softmax (the (L, S) scores never
     exist).  Operands are split around the thread's activation exponent; a value beyond its range ORs ops.overflow_flag.  Inputs
     that need gradients raise NotImplementedError (vit_attention_train is the form with gradients).  vit_attention_planes is the
-    same kernel on the head planes the qkv Linear writes."""
+    same kernel on the head planes the qkv Linear writes.  plain16=True: far_vit_attention_f16 -- one fp16 value per operand and per
+    probability, fp32 softmax; narrower than the reference (ViTEss.set_precision), same checks and edge cases."""
     Z, L, S, C = _vit_views(q, k, v, nhead, 'vit_attention', other='ops.full_attention')
     q, k, v = q.contiguous(), k.contiguous(), v.contiguous()
-    return _vit_attention_launch(q, k, v, Z, L, S, nhead, (L * C, 64, C), (S * C, 64, C))
+    return _vit_attention_launch(q, k, v, Z, L, S, nhead, (L * C, 64, C), (S * C, 64, C), plain16=plain16)
 
-def vit_attention_planes(planes, nhead):
+def vit_attention_planes(planes, nhead, plain16=False):
     """K23 on the head planes ops.linear_f16s(x, qkv, out_planes=3 * nhead) writes: planes (3 nhead, Z, N, 64) fp32 contiguous --
     plane h is q of head h, nhead + h is k, 2 nhead + h is v (the layout K2 reads in place; no copy here either).  Returns
-    (Z, N, nhead * 64) with the heads concatenated: what the `proj` Linear reads.  Checks and refusals as vit_attention."""
+    (Z, N, nhead * 64) with the heads concatenated: what the `proj` Linear reads.  Checks, refusals and plain16 as vit_attention."""
     _on_gpu(planes)
     if planes.dim() != 4 or planes.shape[0] != 3 * nhead or planes.shape[3] != 64 or not planes.is_contiguous():
         raise _lib.FarHipError(f'vit_attention_planes: planes (3 * nhead, Z, N, 64) contiguous, head dim 64 only (K23); got '
                                f'{tuple(planes.shape)} for {nhead} heads')
     _, Z, N, _ = planes.shape
     st = (N * 64, Z * N * 64, 64)
-    return _vit_attention_launch(planes[:nhead], planes[nhead:2 * nhead], planes[2 * nhead:], Z, N, N, nhead, st, st)
+    return _vit_attention_launch(planes[:nhead], planes[nhead:2 * nhead], planes[2 * nhead:], Z, N, N, nhead, st, st, plain16=plain16)
 
 def _vit_views(q, k, v, nhead, what, other='ops.full_attention_train'):
     """The checks K23's front ends share on (Z, L | S, nhead * 64) fp32 GPU tensors -> (Z, L, S, C); `other`: the op the message

@@ -500,7 +500,8 @@ def stem_train(img, weight):
 
 def conv_valid(x, pack, residual=None, act='none'):
     """K24.  x (N, H, W, Cin) fp32 contiguous -> act(conv5x5_valid(x) * scale + shift (+ residual)) as (N, H - 4, W - 4, Cout) for a
-    PackedConvValid; act 'none' or 'relu'; residual in the output's layout.  Takes part in the activation-range guard as K9 does."""
+    PackedConvValid; act 'none' or 'relu'; residual in the output's layout.  Takes part in the activation-range guard as K9 does.
+    A pack built with split=False runs far_conv_valid_f16 (plain fp16 operands, narrower than the reference) -- the same contract."""
     lib = _lib.load()
     if not isinstance(pack, PackedConvValid):
         raise _lib.FarHipError('conv_valid takes a PackedConvValid')
@@ -515,10 +516,11 @@ def conv_valid(x, pack, residual=None, act='none'):
     y = torch.empty(N, H - k + 1, W - k + 1, pack.Cout, dtype=torch.float32, device=x.device)
     if residual is not None and (tuple(residual.shape) != tuple(y.shape) or not residual.is_contiguous()):
         raise _lib.FarHipError(f'conv_valid: `residual` must be a contiguous {tuple(y.shape)} tensor')
-    rc = lib.far_conv_valid_f16s(_p(x, torch.float32), _p(pack.packed), _p(pack.scale), _p(pack.shift, torch.float32), _p(residual, torch.float32),
-                                 _p(y), N, H, W, Cin, pack.Cout, k, _ACT[act], activation_exponent_value(), overflow_flag(x.device).data_ptr(),
-                                 _stream())
-    _lib.check(rc, 'far_conv_valid_f16s')
+    entry = 'far_conv_valid_f16s' if pack.split else 'far_conv_valid_f16'          # a PackedConvValid(split=False): plain fp16 operands
+    rc = getattr(lib, entry)(_p(x, torch.float32), _p(pack.packed), _p(pack.scale), _p(pack.shift, torch.float32), _p(residual, torch.float32),
+                             _p(y), N, H, W, Cin, pack.Cout, k, _ACT[act], activation_exponent_value(), overflow_flag(x.device).data_ptr(),
+                             _stream())
+    _lib.check(rc, entry)
     return y
 
 def _valid_bwd_shapes(what, x_shape, dy, Cin, Cout):

@@ -153,12 +153,18 @@ class PackedConvValid:
     """Weights of one K x K unpadded stride-1 convolution (K = 5) in K24's packed split-fp16 image, plus the folded epilogue vectors:
     the same constructor meaning as PackedConv (scale / shift: the inference BatchNorm as a per-channel affine map, a convolution
     bias folded into shift by the caller).  dgrad=True packs the image of the layer's input-gradient convolution -- channels
-    exchanged, taps reversed -- with pack_scale, the two device floats of the forward image of the same weight."""
+    exchanged, taps reversed -- with pack_scale, the two device floats of the forward image of the same weight.  split=False packs the
+    plain-fp16 image (one fp16 value per weight, half the bytes) and makes ops.conv_valid launch far_conv_valid_f16: 16-bit operands,
+    narrower than the reference (ViTEss.set_precision), forward only -- with dgrad=True it raises."""
 
-    stride, split = 1, True
+    stride = 1
 
-    def __init__(self, weight, scale=None, shift=None, dgrad=False, pack_scale=None):
+    def __init__(self, weight, scale=None, shift=None, dgrad=False, pack_scale=None, split=True):
         lib = _lib.load()
+        self.split = bool(split)
+        if dgrad and not self.split:
+            raise _lib.FarHipError("K24's input gradient has no plain-fp16 form: PackedConvValid(split=False) is forward only "
+                                   '(far_conv_valid_f16); the dgrad image is split-fp16 (far_conv_valid_dgrad_f16s)')
         w = weight.detach()
         if w.dim() != 4 or w.shape[2] != w.shape[3]:
             raise _lib.FarHipError(f'K24 takes a (Cout, Cin, k, k) weight, got {tuple(w.shape)}')
@@ -170,9 +176,10 @@ class PackedConvValid:
             raise _lib.FarHipError("K24's forward image computes its own pack_scale")
         w = w.contiguous().float()
         self.Cout, self.Cin, self.ksize, self.dgrad = int(w.shape[0]), int(w.shape[1]), int(w.shape[2]), bool(dgrad)
-        nbytes = int(lib.far_conv_valid_packed_bytes(self.Cin, self.Cout, self.ksize))
+        size_query = lib.far_conv_valid_packed_bytes if self.split else lib.far_conv_valid_f16_packed_bytes
+        nbytes = int(size_query(self.Cin, self.Cout, self.ksize))
         if nbytes == 0:
-            raise _lib.FarHipError(f'K24 (far_conv_valid_f16s) covers 5x5 kernels with Cin and Cout multiples of 32, got a weight of shape '
+            raise _lib.FarHipError(f'K24 ({"far_conv_valid_f16s" if self.split else "far_conv_valid_f16"}) covers 5x5 kernels with Cin and Cout multiples of 32, got a weight of shape '
                                    f'{tuple(w.shape)}')
         self.packed = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
         self._own_scale = not dgrad
@@ -195,9 +202,10 @@ class PackedConvValid:
             _lib.check(rc, 'far_conv_valid_pack_dgrad_f32')
         else:
             _lib.check(lib.far_weight_scale_f32(_p(w, torch.float32), w.numel(), _p(self.pack_scale), _stream()), 'far_weight_scale_f32')
-            rc = lib.far_conv_valid_pack_f32(_p(w), self.Cin, self.Cout, self.ksize, _p(self.pack_scale), _p(self.packed),
-                                             _p(self._base) if self._base is not None else None, _p(self.scale), _stream())
-            _lib.check(rc, 'far_conv_valid_pack_f32')
+            entry = 'far_conv_valid_pack_f32' if self.split else 'far_conv_valid_pack_f16'
+            rc = getattr(lib, entry)(_p(w), self.Cin, self.Cout, self.ksize, _p(self.pack_scale), _p(self.packed),
+                                     _p(self._base) if self._base is not None else None, _p(self.scale), _stream())
+            _lib.check(rc, entry)
         self._w = w
         return self
 

@@ -37,7 +37,11 @@ GELU and the residual adds are elementwise torch ops.  The CrossBlock trains on 
 containers run under autograd (the package's convention for them, far_amd/_vendor.py).  `pose_loss` is the reference's loss;
 far_amd.optim (K20) is the optimizer side.  The no-grad path is the same code and the same bits whatever the switch says.
 
-Not built (each raises NotImplementedError): training the extractor's ResNet front (K25 / K26 have no backward), dropout and drop-path (0 in every script), per-sample intrinsics, and
+16-bit operands are opt-in and inference only, modelled on LoFTR.set_precision: `ViTEss.set_precision('fp16')` (or a set of
+ViTEss.STAGES names) runs the extractor's K9 / K24 launches, the Blocks' Linear layers, K23 (far_vit_attention_f16) and the CrossBlock
+on plain fp16 operands.  Narrower than the reference; 'fp32' stays the default and the only mode held to the reference's bars.
+
+Not built (each raises NotImplementedError): 16-bit training (a call that needs gradients with a precision stage on), training the extractor's ResNet front (K25 / K26 have no backward), dropout and drop-path (0 in every script), per-sample intrinsics, and
 the pooled-conv ablation (fusion_transformer=False).
 
 Pair order: the reference keeps the two images of pair b in rows 2b, 2b + 1 of a (2B, N, C) tensor; this package's CrossBlock takes
@@ -129,6 +133,8 @@ class Attention(nn.Module):
     in its epilogue).  Head dim 64 only.  forward_train is the form with gradients (block_training)."""
 
     block_training = False       # True: gradients run K23's training forward + HIP backward; False: a call that needs them raises
+    split_operands = True        # inference: K9 operand precision of qkv / proj (False: plain fp16, ViTEss.set_precision 'blocks_dense')
+    plain16 = False              # inference: K23 on plain fp16 operands (far_vit_attention_f16; ViTEss.set_precision 'blocks_attn')
 
     def __init__(self, dim, num_heads=8, qkv_bias=False, attn_drop=0., proj_drop=0.):
         super().__init__()
@@ -143,10 +149,11 @@ class Attention(nn.Module):
     def forward(self, x, residual=None):
         pk = self.__dict__.setdefault('_packs', ops.PackCache())
         qkv_t = [self.qkv.weight] + ([self.qkv.bias] if self.qkv.bias is not None else [])
-        pq = pk.get('qkv', qkv_t, lambda: ops.PackedConv(self.qkv.weight, None, self.qkv.bias))
-        pp = pk.get('proj', [self.proj.weight, self.proj.bias], lambda: ops.PackedConv(self.proj.weight, None, self.proj.bias))
+        sp = self.split_operands
+        pq = pk.get(('qkv', sp), qkv_t, lambda: ops.PackedConv(self.qkv.weight, None, self.qkv.bias, split=sp))
+        pp = pk.get(('proj', sp), [self.proj.weight, self.proj.bias], lambda: ops.PackedConv(self.proj.weight, None, self.proj.bias, split=sp))
         planes = ops.linear_f16s(x.contiguous(), pq, out_planes=3 * self.num_heads)          # (3h, Z, N, 64)
-        a = ops.vit_attention_planes(planes, self.num_heads)                                # (Z, N, C), heads concatenated
+        a = ops.vit_attention_planes(planes, self.num_heads, plain16=self.plain16)          # (Z, N, C), heads concatenated
         return ops.linear_f16s(a, pp, residual=None if residual is None else residual.contiguous())
 
     def forward_train(self, x):
@@ -358,6 +365,58 @@ class ViTEss(nn.Module):
 
     update_intrinsics = staticmethod(update_intrinsics)
 
+    # Operand precision of the inference path, as LoFTR.set_precision: the stages that run on plain fp16 operands (one fp16 value per
+    # operand, fp32 accumulation) instead of split-fp16 pairs.  NARROWER THAN THE REFERENCE: 'fp32' (no stage) is the only mode held
+    # to the reference's bars and the default; the 16-bit stages exist for users who have accepted 16-bit operands, and cost
+    # deviation (README, 8-Point-ViT section).  The LayerNorms (K6), the head's Linear layers (K15), K25 and K26 stay exact.
+    STAGES = ('extractor',     # resnet.layer1 / layer2 and extractor_final_conv.conv1 on K9 plain fp16 (PackedConv(split=False);
+                               # conv_nhwc then never takes K17), conv2 / downsample.0 on far_conv_valid_f16.  K25 (stem) and K26 unchanged.
+              'blocks_dense',  # qkv, proj, fc1, fc2 of the five Blocks: K9 plain fp16
+              'blocks_attn',   # K23 -> far_vit_attention_f16
+              'cross')         # the CrossBlock: CrossAttention.plain16 (qkv projection + far_emm_pv_f16) and its Mlp
+    MODES = {'fp32': (), 'fp16': STAGES}
+    PRECISIONS = tuple(MODES)
+    precision_stages = ()      # stages on 16-bit operands (set_precision); () = fp32-grade everywhere = the parity configuration
+    extractor_split = True     # False: the extractor's K9 / K24 launches on plain fp16 operands ('extractor')
+
+    def set_precision(self, mode):
+        """mode: a name of MODES ('fp32': every product on split-fp16 operand pairs, fp32-grade, the parity configuration and the
+        default; 'fp16': every stage on plain fp16 operands) or an iterable of STAGES names (the stages that run on 16-bit operands).
+        Inference only: a call that needs gradients while a stage is on raises NotImplementedError (training stays fp32-grade);
+        under torch.no_grad(), or in .eval() without gradients, the stages apply whatever the training switches say.  Sets
+        `precision_stages` (a tuple in STAGES order) and plain attributes on the submodules; the state dict does not change, and
+        every weight image is cached under its operand class, so going back to 'fp32' gives the bits from before.  Returns self."""
+        if isinstance(mode, str):
+            if mode not in self.MODES:
+                raise ValueError(f'precision must be one of {self.PRECISIONS} or an iterable of {self.STAGES}')
+            st = set(self.MODES[mode])
+        else:
+            try:
+                st = set(mode)
+            except TypeError:
+                raise ValueError(f'precision must be one of {self.PRECISIONS} or an iterable of {self.STAGES}') from None
+            if not all(isinstance(s, str) for s in st) or not st <= set(self.STAGES):
+                raise ValueError(f'unknown precision stages {sorted(map(str, st - set(self.STAGES)))}; known: {self.STAGES} '
+                                 f'(or a mode: {self.PRECISIONS})')
+        if 'extractor' in st and not self.has_extractor:
+            raise ValueError("precision stage 'extractor': this model was built without extractor=True -- it has no extractor to "
+                             f'switch; the stages of the trunk are {self.STAGES[1:]}')
+        self.precision_stages = tuple(s for s in self.STAGES if s in st)
+        self.extractor_split = 'extractor' not in st
+        for blk in self.fusion_transformer.blocks:
+            if isinstance(blk, Block):
+                blk.attn.split_operands = blk.mlp.split_operands = 'blocks_dense' not in st
+                blk.attn.plain16 = 'blocks_attn' in st
+            else:                                                   # the CrossBlock
+                blk.cross_attn.plain16 = 'cross' in st
+                blk.mlp.split_operands = 'cross' not in st
+        return self
+
+    def _precision_no_grad(self, what):
+        return NotImplementedError(f'ViTEss.{what}: gradients are wanted while the precision stages {self.precision_stages} are on -- '
+                                   "the 16-bit-operand stages are inference only (no 16-bit backward kernels exist; training stays "
+                                   "fp32-grade): call set_precision('fp32') before training, or run under torch.no_grad()")
+
     def set_block_training(self, on=True):
         """Opt in to (or out of) gradients through the trunk: sets `block_training` on the FusionTransformer, its Blocks and their
         Attention modules -- plain instance attributes, the state dict's keys do not change.  Returns self."""
@@ -418,12 +477,14 @@ class ViTEss(nn.Module):
         """One BasicBlock on K9 / K17: relu(bn1(conv1(x))), then relu(bn2(conv2(.)) + shortcut) with the add and the ReLU in conv2's
         epilogue; the 1x1 stride-2 shortcut reads x[:, ::2, ::2] in place (in_stride = 2)."""
         st = blk.conv1.stride[0]
-        fold = lambda conv, bn, **kw: (lambda: ops.PackedConv(conv.weight, *_fold(conv, bn), **kw))
-        p1 = pk.get(name + '.conv1', _fold_tensors(blk.conv1, blk.bn1), fold(blk.conv1, blk.bn1, stride=st))
-        p2 = pk.get(name + '.conv2', _fold_tensors(blk.conv2, blk.bn2), fold(blk.conv2, blk.bn2))
+        sp = self.extractor_split                                   # False: plain fp16 operands (conv_nhwc then never takes K17)
+        fold = lambda conv, bn, **kw: (lambda: ops.PackedConv(conv.weight, *_fold(conv, bn), split=sp, **kw))
+        p1 = pk.get((name + '.conv1', sp), _fold_tensors(blk.conv1, blk.bn1), fold(blk.conv1, blk.bn1, stride=st))
+        p2 = pk.get((name + '.conv2', sp), _fold_tensors(blk.conv2, blk.bn2), fold(blk.conv2, blk.bn2))
         y = ops.conv_nhwc(x, p1, act='relu')
         if blk.downsample is not None:
-            pd = pk.get(name + '.downsample', _fold_tensors(blk.downsample[0], blk.downsample[1]), fold(blk.downsample[0], blk.downsample[1]))
+            pd = pk.get((name + '.downsample', sp), _fold_tensors(blk.downsample[0], blk.downsample[1]),
+                        fold(blk.downsample[0], blk.downsample[1]))
             x = ops.conv_nhwc(x, pd, in_stride=st)
         return ops.conv_nhwc(y, p2, residual=x, act='relu')
 
@@ -458,6 +519,8 @@ class ViTEss(nn.Module):
                 raise NotImplementedError('ViTEss: gradients into extractor_final_conv.* are wanted (set_extractor_training()) with the '
                                           'block in .eval() mode: its training kernels use batch statistics -- call .train(), '
                                           'set_extractor_training(on=False), or run under torch.no_grad()')
+            if wanted and self.precision_stages:
+                raise self._precision_no_grad('extract_features')
             train_final = wanted
         if not images.is_cuda:
             raise ops._lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
@@ -475,10 +538,13 @@ class ViTEss(nn.Module):
             x = self._final_block_train(x)
             return x.reshape(x.shape[0], self.num_patches, DIM), grid_intrinsics
         with torch.no_grad():
-            p1 = pk.get('final.conv1', _fold_tensors(fc.conv1, fc.norm1), lambda: ops.PackedConv(fc.conv1.weight, *_fold(fc.conv1, fc.norm1)))
-            p2 = pk.get('final.conv2', _fold_tensors(fc.conv2, fc.norm2), lambda: ops.PackedConvValid(fc.conv2.weight, *_fold(fc.conv2, fc.norm2)))
-            pd = pk.get('final.downsample', _fold_tensors(fc.downsample[0], fc.norm3),
-                        lambda: ops.PackedConvValid(fc.downsample[0].weight, *_fold(fc.downsample[0], fc.norm3)))
+            sp = self.extractor_split                               # False: K9 / K24 on plain fp16 operands (set_precision 'extractor')
+            p1 = pk.get(('final.conv1', sp), _fold_tensors(fc.conv1, fc.norm1),
+                        lambda: ops.PackedConv(fc.conv1.weight, *_fold(fc.conv1, fc.norm1), split=sp))
+            p2 = pk.get(('final.conv2', sp), _fold_tensors(fc.conv2, fc.norm2),
+                        lambda: ops.PackedConvValid(fc.conv2.weight, *_fold(fc.conv2, fc.norm2), split=sp))
+            pd = pk.get(('final.downsample', sp), _fold_tensors(fc.downsample[0], fc.norm3),
+                        lambda: ops.PackedConvValid(fc.downsample[0].weight, *_fold(fc.downsample[0], fc.norm3), split=sp))
             y = ops.conv_valid(ops.conv_nhwc(x, p1, act='relu'), p2, act='relu')                        # extractor.py:53-54
             x = ops.conv_valid(x, pd, residual=y, act='relu')                                            # :56-57, :65 -> (2B, 24, 24, 192)
         # model.py:156-161: (2B, 192, 576) permuted to (2B, 576, 192) is the NHWC tensor itself; the channel cut [:, :192] is a no-op
@@ -489,6 +555,8 @@ class ViTEss(nn.Module):
         taps (tests): receives each block's output, Blocks in the reference's pair order."""
         if features.dim() != 3 or features.shape[0] % 2 or tuple(features.shape[1:]) != (self.num_patches, DIM):
             raise ValueError(f'features: (2B, {self.num_patches}, {DIM}) with rows (2b, 2b + 1) = pair b, got {tuple(features.shape)}')
+        if self.precision_stages and ag.needs_grad(features, self.fusion_transformer.pos_embed):
+            raise self._precision_no_grad('trunk')
         cam = None if intrinsics is None else _one_camera(intrinsics)
         got = None if taps is None else []
         out = self.fusion_transformer(interleaved_to_concatenated(features.float()), cam, got)

@@ -30,7 +30,7 @@ typedef struct ihipStream_t* far_stream_t; /* == hipStream_t */
 
 /* ABI version of this header; bumped when a signature changes (2: activation exponent / overflow flag of K9, K13, K14; 3: the
  * far_wino_* / far_conv3x3_wino_f32 entry points, 16 tuning keys; 4: far_upsample2x_bwd_f32, far_fine_scatter_det_f32, far_bn_train_*, far_adamw_*; 5: far_linear_kv_f16s, far_linear_q_apply_f16s,
- * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way, and so were far_grad_norm_workspace_bytes, far_grad_norm_f32, far_grad_clip_scale_f32 and far_adam_step_f32, and the five far_bn_sync_*_f32 entry points, and the far_conv_valid_* / far_stem_rgb_* / far_maxpool3x3s2_nhwc_f32 entry points of K24-K26, and K24's backward: far_conv_valid_pack_dgrad_f32, far_conv_valid_dgrad_f16s, far_conv_valid_wgrad_ws_bytes, far_conv_valid_wgrad_f16s -- pure additions, which tests/test_dense_spvs_cpu.py holds at 8).  far_amd/_lib.py refuses a library whose version differs. */
+ * far_linear_gather_f16s, far_linear_attention_apply_f32, far_prior_from_pose_f32; 6: far_ransac_f64, far_eightpoint_f64, far_decompose_essential_f64, far_build_id; 7: far_emm_pv_f16, far_attn_block_f16, far_mlp_fused_f16; far_linear_kv_f16s / far_linear_q_apply_f16s accept split = 0; 8: far_coarse_match_sinkhorn_f16s; far_full_attention_f16s was added under 8 -- no existing signature changed, and a library without it is refused by its build id and the symbol lookup; far_full_attention_train_f16s, far_full_attention_bwd_f16s and far_full_attention_bwd_workspace_bytes were added under 8 in the same way, and so were far_grad_norm_workspace_bytes, far_grad_norm_f32, far_grad_clip_scale_f32 and far_adam_step_f32, and the five far_bn_sync_*_f32 entry points, and the far_conv_valid_* / far_stem_rgb_* / far_maxpool3x3s2_nhwc_f32 entry points of K24-K26, and K24's backward: far_conv_valid_pack_dgrad_f32, far_conv_valid_dgrad_f16s, far_conv_valid_wgrad_ws_bytes, far_conv_valid_wgrad_f16s, and the plain-fp16 siblings of K23 / K24: far_vit_attention_f16, far_conv_valid_f16_packed_bytes, far_conv_valid_pack_f16, far_conv_valid_f16 -- pure additions, which tests/test_dense_spvs_cpu.py holds at 8).  far_amd/_lib.py refuses a library whose version differs. */
 int far_abi_version(void);
 /* Id of the sources the library was built from: sha256/16 over far_amd/csrc/* and the compiler flags (far_amd/build.py
  * source_id()).  far_amd/_lib.py refuses a library whose id differs from the sources it sits next to. */
@@ -358,6 +358,17 @@ int far_full_attention_f16s(const float* q, const float* k, const float* v, int 
 int far_vit_attention_f16s(const float* q, const float* k, const float* v, int Z, int L, int S, int H, int D, long q_img, long q_head,
                            long q_row, long kv_img, long kv_head, long kv_row, int act_exp, float* out, int* overflow,
                            far_stream_t stream);
+
+/* K23 on plain fp16 operands (vit_attention_f16.hip): far_vit_attention_f16s with ONE fp16 value per operand -- the same operator,
+ * arguments, addressing, launch geometry, checks and return codes.  Every q / k / v value enters as fp16(x 2^act_exp) (no lo part),
+ * one MFMA per k-step instead of three; the softmax stays in fp32 (integer row reference, the row sum takes the unrounded
+ * probabilities with Kahan compensation), and the probabilities enter P V as fp16(p), rounded once: against the softmax attention of
+ * the ROUNDED operands the output is within 2^-11 max|v| (+ fp32 accumulation).  Narrower than the reference: the 16-bit-operand
+ * class of ViTEss.set_precision, never the parity configuration.  Inference only (the backward is split-fp16 only).  No workspace,
+ * no float atomics, run-to-run and batch-independent bits as far_vit_attention_f16s. */
+int far_vit_attention_f16(const float* q, const float* k, const float* v, int Z, int L, int S, int H, int D, long q_img, long q_head,
+                          long q_row, long kv_img, long kv_head, long kv_row, int act_exp, float* out, int* overflow,
+                          far_stream_t stream);
 
 /* K23 under autograd (vit_attention_f16s.hip, vit_attention_bwd_f16s.hip).
  * far_vit_attention_train_f16s: far_vit_attention_f16s -- the same launch, the same `out` bits -- that also writes lse [Z][H][L] fp32:
@@ -805,6 +816,17 @@ int far_conv_valid_dgrad_f16s(const float* dy, const void* packed_dgrad, const f
 long far_conv_valid_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int ksize);
 int far_conv_valid_wgrad_f16s(const float* x, const float* dy, int N, int H, int W, int Cin, int Cout, int ksize, int act_exp,
                               const float* dy_scale_dev, void* ws, long ws_bytes, float* dw, int* overflow, far_stream_t stream);
+/* K24 on plain fp16 operands (conv_valid_f16.hip): the same operator, shapes, epilogue, checks and return codes with ONE fp16 value
+ * per activation (fp16(x 2^act_exp)) and per weight (fp16(w pack_scale[0])), fp32 accumulation, one MFMA per (tile, k-step) instead
+ * of three.  far_conv_valid_f16_packed_bytes: half of far_conv_valid_packed_bytes (0 for a shape not covered);
+ * far_conv_valid_pack_f16 writes that image ([chunk][tap][k-step][N-tile][lane][8], one plane) and the same scale vector;
+ * far_conv_valid_f16 takes it as `packed`.  Forward only.  Narrower than the reference (ViTEss.set_precision), never the parity
+ * configuration.  Deterministic; image n's output does not depend on N; both launch forms give the same bits. */
+size_t far_conv_valid_f16_packed_bytes(int Cin, int Cout, int ksize);
+int far_conv_valid_pack_f16(const float* w, int Cin, int Cout, int ksize, const float* pack_scale, void* packed, const float* base_scale,
+                            float* scale_vec, far_stream_t stream);
+int far_conv_valid_f16(const float* x, const void* packed, const float* scale, const float* shift, const float* res, float* y, long N,
+                       int H, int W, int Cin, int Cout, int ksize, int act, int act_exp, int* overflow, far_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
  * K25  RGB stem of the 8-Point-ViT's extractor, one launch; K26  max-pool 3x3 stride 2 pad 1 (NHWC, exact)

@@ -10,7 +10,12 @@ B = 32 pairs (2 and 64 images of 480 x 640):
   * end to end: ViTEss.forward(images) next to the torch extractor followed by today's forward_features.
 
 Timing as tools/vit8pt_time.py: HIP events around groups of launches, every leg warmed up, the legs ALTERNATED round by round, medians
-over the rounds with the min .. max spread.  Prints a table and one JSON line.  Usage: python tools/vit8pt_extractor_time.py [--rounds N]"""
+over the rounds with the min .. max spread.
+--precision fp16: the 16-bit-operand mode of ViTEss.set_precision next to the default one IN THE SAME PROCESS on the same inputs -- K24 on
+plain fp16 operands (far_conv_valid_f16, leg k24_f16) alternating with K24, and extract_features / forward(images) of a second model on
+the same weights in mode 'fp16' (legs *_fp16) alternating with the fp32-grade model; deviations are printed next to the gains (the mode
+is narrower than the reference).
+Prints a table and one JSON line.  Usage: python tools/vit8pt_extractor_time.py [--rounds N] [--precision fp32|fp16]"""
 import argparse
 import json
 import os
@@ -43,7 +48,7 @@ def stats(r):
     return {name: {'median_ms': m, 'min_ms': lo, 'max_ms': hi} for name, (m, lo, hi) in r.items()}
 
 
-def extractor_case(m, ref, inp, B, rounds):
+def extractor_case(m, ref, inp, B, rounds, m16=None):
     from tests import vit8pt_extractor_inputs as ei
     g = torch.Generator(device='cuda').manual_seed(B)
     images = torch.randint(0, 256, (B, 2, 3, *SIZE), device='cuda', generator=g).float()
@@ -53,7 +58,7 @@ def extractor_case(m, ref, inp, B, rounds):
     with torch.no_grad():
         feats = m.extract_features(images)[0]                                  # builds the packs
         pk, rn, fc = m._extractor_packs._store, m.resnet, m.extractor_final_conv
-        get = lambda k: pk[k][1]
+        get = lambda k: pk[k if k == 'stem' else (k, m.extractor_split)][1]
         s = ops.stem_rgb(flat, get('stem'))
         p = ops.maxpool3x3s2(s)
         x = p
@@ -85,12 +90,20 @@ def extractor_case(m, ref, inp, B, rounds):
             'torch_fp32_extractor': lambda: ref.extract_features(images),
             'forward_images': lambda: m(images, intr, loftr_num_corr=ncorr, loftr_preds=preds),
             'torch_extractor_then_forward_features': lambda: m.forward_features(ref.extract_features(images).contiguous(), grid, ncorr, preds)}
+    extra = {}
+    if m16 is not None:
+        legs['extract_features_fp16'] = lambda: m16.extract_features(images)
+        legs['forward_images_fp16'] = lambda: m16(images, intr, loftr_num_corr=ncorr, loftr_preds=preds)
     r = alternate({k: nograd(v) for k, v in legs.items()}, rounds, target_ms=40.0)
     dev = float((feats - ref.extract_features(images)).abs().max())
-    return {'B': B, 'images': 2 * B, 'image_size': list(SIZE), 'max_abs_diff_of_the_features_vs_torch_fp32': dev, **stats(r)}
+    if m16 is not None:
+        with torch.no_grad():
+            extra = {'max_abs_diff_of_the_features_vs_torch_fp32_fp16': float((m16.extract_features(images)[0] - ref.extract_features(images)).abs().max()),
+                     'max_abs_features': float(feats.abs().max())}
+    return {'B': B, 'images': 2 * B, 'image_size': list(SIZE), 'max_abs_diff_of_the_features_vs_torch_fp32': dev, **extra, **stats(r)}
 
 
-def conv5_case(cin, B, rounds):
+def conv5_case(cin, B, rounds, fp16=False):
     N, cout = 2 * B, 192
     g = torch.Generator(device='cuda').manual_seed(cin + B)
     x = torch.randn(N, 28, 28, cin, device='cuda', generator=g)
@@ -106,40 +119,62 @@ def conv5_case(cin, B, rounds):
         return ops.linear_f16s(cols, lin)
     legs = {'k24': lambda: ops.conv_valid(x, pack), 'torch_fp32_conv2d_nchw': lambda: F.conv2d(xn, w),
             'torch_fp32_conv2d_channels_last': lambda: F.conv2d(xcl, wcl), 'unfold_plus_k9_linear': unfold_k9}
+    extra = {}
+    if fp16:
+        pack16 = ops.PackedConvValid(w, split=False)
+        legs = {'k24': legs['k24'], 'k24_f16': lambda: ops.conv_valid(x, pack16), **legs}
     with torch.no_grad():
         r = alternate(legs, rounds)
+        if fp16:
+            extra = {'max_abs_diff_vs_conv2d_f16': float((ops.conv_valid(x, pack16) - F.conv2d(xn, w).permute(0, 2, 3, 1)).abs().max())}
         dev = float((ops.conv_valid(x, pack) - F.conv2d(xn, w).permute(0, 2, 3, 1)).abs().max())
         dev_u = float((unfold_k9().reshape(N, 24, 24, cout) - F.conv2d(xn, w).permute(0, 2, 3, 1)).abs().max())
     floor = 3 * 2.0 * N * 576 * 25 * cin * cout / MFMA_RATE * 1e3
     return {'B': B, 'images': N, 'Cin': cin, 'Cout': cout, 'workgroups': N * 3 * (3 if N * 3 < 128 else 1), 'mfma_floor_ms': floor, 'max_abs_diff_vs_conv2d': dev,
-            'max_abs_diff_of_unfold_route_vs_conv2d': dev_u, **stats(r)}
+            'max_abs_diff_of_unfold_route_vs_conv2d': dev_u, **extra, **stats(r)}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=11)
+    ap.add_argument('--precision', choices=('fp32', 'fp16'), default='fp32',
+                    help='fp16: the 16-bit-operand kernels / mode next to the default ones, in the same process')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('vit8pt_extractor_time needs a GPU: nothing is timed without one')
-    res = {'tool': 'vit8pt_extractor_time', 'device': torch.cuda.get_device_name(), 'rounds': a.rounds, 'conv5x5': [], 'extractor': []}
+    fp16 = a.precision == 'fp16'
+    res = {'tool': 'vit8pt_extractor_time', 'device': torch.cuda.get_device_name(), 'rounds': a.rounds, 'precision': a.precision, 'conv5x5': [],
+           'extractor': []}
     fmt = lambda d: f'{d["median_ms"]:9.4f} ms  ({d["min_ms"]:.4f} .. {d["max_ms"]:.4f})'
     for B in (1, 32):
         for cin in (128, 192):
-            c = conv5_case(cin, B, a.rounds)
+            c = conv5_case(cin, B, a.rounds, fp16)
             res['conv5x5'].append(c)
             print(f'# 5x5 valid convolution {cin} -> 192, 28 x 28 -> 24 x 24, B = {B} ({c["images"]} images, {c["workgroups"]} workgroups), MFMA floor '
                   f'{c["mfma_floor_ms"]:.4f} ms; max |K24 - conv2d| {c["max_abs_diff_vs_conv2d"]:.2e}')
-            for leg in ('k24', 'torch_fp32_conv2d_nchw', 'torch_fp32_conv2d_channels_last', 'unfold_plus_k9_linear'):
+            for leg in (n for n in ('k24', 'k24_f16', 'torch_fp32_conv2d_nchw', 'torch_fp32_conv2d_channels_last', 'unfold_plus_k9_linear') if n in c):
                 print(f'  {leg:34s} {fmt(c[leg])}' + (f'   x{c[leg]["median_ms"] / c["k24"]["median_ms"]:.2f} of K24' if leg != 'k24' else
                                                     f'   {c["mfma_floor_ms"] / c[leg]["median_ms"]:.1%} of the MFMA floor'))
+            if fp16:
+                print(f'  max |out - fp32 conv2d|: K24 {c["max_abs_diff_vs_conv2d"]:.2e}, plain fp16 {c["max_abs_diff_vs_conv2d_f16"]:.2e}')
     m, ref, inp = models()
+    m16 = None
+    if fp16:
+        m16 = models()[0].set_precision('fp16')
     for B in (1, 32):
-        c = extractor_case(m, ref, inp, B, a.rounds)
+        c = extractor_case(m, ref, inp, B, a.rounds, m16)
         res['extractor'].append(c)
         print(f'# extractor B = {B} ({c["images"]} images of {SIZE[0]} x {SIZE[1]}); max |features - torch fp32| {c["max_abs_diff_of_the_features_vs_torch_fp32"]:.2e}')
-        for leg in ('extract_features', 'k25_stem_rgb', 'k26_maxpool', 'k9_k17_layers', 'k24_conv2_192_192', 'k24_downsample_128_192',
-                    'torch_fp32_extractor', 'forward_images', 'torch_extractor_then_forward_features'):
+        if fp16:
+            print(f'  max |features - torch fp32| in mode fp16: {c["max_abs_diff_of_the_features_vs_torch_fp32_fp16"]:.2e} (max |features| {c["max_abs_features"]:.2f})')
+        for leg in (n for n in ('extract_features', 'extract_features_fp16', 'k25_stem_rgb', 'k26_maxpool', 'k9_k17_layers', 'k24_conv2_192_192',
+                                'k24_downsample_128_192', 'torch_fp32_extractor', 'forward_images', 'forward_images_fp16',
+                                'torch_extractor_then_forward_features') if n in c):
             ratio = ''
+            if leg == 'extract_features_fp16':
+                ratio = f'   x{c[leg]["median_ms"] / c["extract_features"]["median_ms"]:.2f} of extract_features'
+            if leg == 'forward_images_fp16':
+                ratio = f'   x{c[leg]["median_ms"] / c["forward_images"]["median_ms"]:.2f} of forward(images)'
             if leg == 'torch_fp32_extractor':
                 ratio = f'   x{c[leg]["median_ms"] / c["extract_features"]["median_ms"]:.2f} of extract_features'
             if leg == 'torch_extractor_then_forward_features':

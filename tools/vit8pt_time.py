@@ -14,7 +14,11 @@
 Timing: HIP events around groups of launches (a group is long enough that the event resolution and the launch gaps do not decide),
 every leg warmed up first, the legs ALTERNATED round by round, medians over the rounds with the min .. max spread.  The MFMA floor
 of K23 is 3 (split products) x 4 L S H 64 Z flop at the 1.71 PFLOP/s that far_mfma_probe_f16 sustains.
-Prints a table and one JSON line.  Usage: python tools/vit8pt_time.py [--rounds N] [--legs inference,train]"""
+--precision fp16 (inference legs): the 16-bit-operand mode of ViTEss.set_precision next to the default one IN THE SAME PROCESS on the
+same inputs -- K23 on plain fp16 operands (far_vit_attention_f16, leg k23_f16) alternating with K23, and forward_features of a second
+model on the same weights with every trunk stage on 16-bit operands (leg far_amd_fp16) alternating with the fp32-grade model; the
+deviation of each from the fp32 torch computation is printed next to the gain (the mode is narrower than the reference).
+Prints a table and one JSON line.  Usage: python tools/vit8pt_time.py [--rounds N] [--legs inference,train] [--precision fp32|fp16]"""
 import argparse
 import json
 import os
@@ -54,7 +58,7 @@ def alternate(legs, rounds, target_ms=30.0):
     return {name: (statistics.median(v), min(v), max(v)) for name, v in ts.items()}
 
 
-def attention_case(B, rounds):
+def attention_case(B, rounds, fp16=False):
     H, N, Z = 3, 576, 2 * B
     g = torch.Generator(device='cuda').manual_seed(B)
     planes = torch.randn(3 * H, Z, N, 64, device='cuda', generator=g) * 1.5
@@ -67,6 +71,8 @@ def attention_case(B, rounds):
     def sdpa():
         return torch.nn.functional.scaled_dot_product_attention(q, k, v).transpose(1, 2).reshape(Z, N, H * 64)
     legs = {'k23': lambda: ops.vit_attention_planes(planes, H), 'torch_fp32_composition': composition}
+    if fp16:
+        legs = {'k23': legs['k23'], 'k23_f16': lambda: ops.vit_attention_planes(planes, H, plain16=True), 'torch_fp32_composition': composition}
     try:                                     # a torch build without an fp32 fused path: the leg is left out, and the table says so
         sdpa()
         legs['torch_fp32_sdpa'] = sdpa
@@ -75,11 +81,12 @@ def attention_case(B, rounds):
     r = alternate(legs, rounds)
     dev = float((ops.vit_attention_planes(planes, H) - composition()).abs().max())
     floor = 3 * 4.0 * N * N * H * 64 * Z / MFMA_RATE * 1e3
-    return {'B': B, 'Z': Z, 'workgroups': Z * H * ((N + 127) // 128), 'mfma_floor_ms': floor, 'max_abs_diff_vs_composition': dev,
+    extra = {'max_abs_diff_vs_composition_f16': float((ops.vit_attention_planes(planes, H, plain16=True) - composition()).abs().max())} if fp16 else {}
+    return {'B': B, 'Z': Z, 'workgroups': Z * H * ((N + 127) // 128), 'mfma_floor_ms': floor, 'max_abs_diff_vs_composition': dev, **extra,
             **{name: {'median_ms': m, 'min_ms': lo, 'max_ms': hi} for name, (m, lo, hi) in r.items()}}
 
 
-def model_case(B, rounds):
+def model_case(B, rounds, fp16=False):
     from far_amd.vit8pt import ViTEss
     from tests import vit8pt_inputs as vi
     from tests import vit8pt_ref as vr
@@ -100,9 +107,21 @@ def model_case(B, rounds):
 
     def theirs():
         return ref.forward_features(feats, vi.VIT_INTRINSICS, ncorr, preds)
-    r = alternate({'far_amd': ours, 'torch_fp32_restatement': theirs}, rounds, target_ms=60.0)
+    legs, extra = {'far_amd': ours, 'torch_fp32_restatement': theirs}, {}
+    if fp16:
+        m16 = ViTEss(vi.vit_args(), inp['pose_mean'], inp['pose_std'])
+        m16.load_state_dict(m.state_dict(), strict=True)
+        m16 = m16.eval().cuda().set_precision(ViTEss.STAGES[1:])              # every stage of the trunk (this model has no extractor)
+
+        def ours16():
+            with torch.no_grad():
+                return m16.forward_features(feats, intr, ncorr, preds)
+        legs = {'far_amd': ours, 'far_amd_fp16': ours16, 'torch_fp32_restatement': theirs}
+    r = alternate(legs, rounds, target_ms=60.0)
     dev = max(float((a - b).abs().max()) for a, b in zip(ours(), theirs()))
-    return {'B': B, 'max_abs_diff_of_the_outputs': dev, **{name: {'median_ms': md, 'min_ms': lo, 'max_ms': hi} for name, (md, lo, hi) in r.items()}}
+    if fp16:
+        extra = {'max_abs_diff_of_the_outputs_fp16': max(float((a - b).abs().max()) for a, b in zip(ours16(), theirs()))}
+    return {'B': B, 'max_abs_diff_of_the_outputs': dev, **extra, **{name: {'median_ms': md, 'min_ms': lo, 'max_ms': hi} for name, (md, lo, hi) in r.items()}}
 
 
 def attention_train_case(B, rounds):
@@ -208,25 +227,33 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rounds', type=int, default=15)
     ap.add_argument('--legs', default='inference,train', help='comma-separated: inference, train')
+    ap.add_argument('--precision', choices=('fp32', 'fp16'), default='fp32',
+                    help='fp16: the 16-bit-operand kernels / mode next to the default ones, in the same process (inference legs)')
     a = ap.parse_args()
     which = set(a.legs.split(','))
     if not torch.cuda.is_available():
         raise SystemExit('vit8pt_time needs a GPU: nothing is timed without one')
-    res = {'tool': 'vit8pt_time', 'device': torch.cuda.get_device_name(), 'rounds': a.rounds, 'attention': [], 'forward_features': []}
+    fp16 = a.precision == 'fp16'
+    res = {'tool': 'vit8pt_time', 'device': torch.cuda.get_device_name(), 'rounds': a.rounds, 'precision': a.precision, 'attention': [],
+           'forward_features': []}
     fmt = lambda d: f'{d["median_ms"]:9.4f} ms  ({d["min_ms"]:.4f} .. {d["max_ms"]:.4f})'
     for B in (1, 32) if 'inference' in which else ():
-        c = attention_case(B, a.rounds)
+        c = attention_case(B, a.rounds, fp16)
         res['attention'].append(c)
         print(f'# attention L = S = 576, H = 3, D = 64, B = {B} (Z = {c["Z"]}, {c["workgroups"]} workgroups), MFMA floor {c["mfma_floor_ms"]:.4f} ms')
-        for leg in (n for n in ('k23', 'torch_fp32_composition', 'torch_fp32_sdpa') if n in c):
+        for leg in (n for n in ('k23', 'k23_f16', 'torch_fp32_composition', 'torch_fp32_sdpa') if n in c):
             print(f'  {leg:26s} {fmt(c[leg])}' + (f'   x{c[leg]["median_ms"] / c["k23"]["median_ms"]:.2f} of K23' if leg != 'k23' else
                                                 f'   {c["mfma_floor_ms"] / c[leg]["median_ms"]:.1%} of the MFMA floor'))
+        if fp16:
+            print(f'  max |out - fp32 composition|: K23 {c["max_abs_diff_vs_composition"]:.2e}, plain fp16 {c["max_abs_diff_vs_composition_f16"]:.2e}')
     for B in (1, 32) if 'inference' in which else ():
-        c = model_case(B, a.rounds)
+        c = model_case(B, a.rounds, fp16)
         res['forward_features'].append(c)
         print(f'# forward_features B = {B} (depth 6, gating, normalized 6d); max |output difference| {c["max_abs_diff_of_the_outputs"]:.2e}')
-        for leg in ('far_amd', 'torch_fp32_restatement'):
+        for leg in (n for n in ('far_amd', 'far_amd_fp16', 'torch_fp32_restatement') if n in c):
             print(f'  {leg:26s} {fmt(c[leg])}' + (f'   x{c[leg]["median_ms"] / c["far_amd"]["median_ms"]:.2f} of far_amd' if leg != 'far_amd' else ''))
+        if fp16:
+            print(f'  max |output - fp32 restatement|: fp32 mode {c["max_abs_diff_of_the_outputs"]:.2e}, 16-bit trunk stages {c["max_abs_diff_of_the_outputs_fp16"]:.2e}')
     if 'train' in which:
         main_train(a, res, fmt)
     print(json.dumps(res))
