@@ -163,6 +163,9 @@ SIGNATURES = {
     'far_stem_rgb_pack_f32': (c_i, [c_p, c_p, c_p, c_p, c_p, c_p]),
     'far_stem_rgb_f16s': (c_i, [c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),                              # K25
     'far_maxpool3x3s2_nhwc_f32': (c_i, [c_p, c_l, c_i, c_i, c_i, c_p, c_p]),                                          # K26
+    'far_stem_conv_rgb_f16s': (c_i, [c_p, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p]),                         # K27
+    'far_upsample2x_pad_f32': (c_i, [c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_p, c_p]),                    # K28
+    'far_elu_f32': (c_i, [c_p, c_l, c_p, c_p]),                                                                       # K28
     'far_pose_pack_f64': (c_i, [c_p] * 8 + [c_i] + [c_p] * 6 + [c_p]),
     'far_pose_features_f32': (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_p]),
     'far_rows_linear_packed_bytes': (c_sz, [c_i, c_i]),

@@ -3,7 +3,7 @@ far_amd/ops.py, split):
 
     _base      streams, pointers, workspaces, the activation-range state
     packs      weight images (PackedConv, PackedWino, PackedConvValid, PackedStemRGB, the pack table, PackCache)
-    conv       K9 / K17 / K10 / K24 / K25 convolutions, K26 max-pool, K19 BatchNorm, K8 upsample-add, K7 affine epilogues
+    conv       K9 / K17 / K10 / K24 / K25 / K27 convolutions, K26 max-pool, K19 BatchNorm, K8 upsample-add, K7 affine epilogues, K28 decoder glue
     linear     K9 in Linear mode (plain, gather, k|v-state, q-apply)
     attention  K5 linear attention, K22 full attention, K6 LayerNorm
     coarse     K1

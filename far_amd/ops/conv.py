@@ -1,4 +1,4 @@
-"""far_amd.ops.conv: K9 / K17 / K10 convolutions (inference + training forms), the extractor's K24 / K25 / K26, BatchNorm K19, FPN upsample-add K8, affine epilogues K7 (one family of the torch-tensor front ends for the C ABI in include/far_hip.h; far_amd/ops/__init__.py
+"""far_amd.ops.conv: K9 / K17 / K10 convolutions (inference + training forms), the extractor's K24 / K25 / K26, the Map-free encoder's K27 / K28, BatchNorm K19, FPN upsample-add K8, affine epilogues K7 (one family of the torch-tensor front ends for the C ABI in include/far_hip.h; far_amd/ops/__init__.py
 re-exports everything under the flat far_amd.ops namespace the rest of the package uses)."""
 import ctypes
 import os
@@ -670,3 +670,70 @@ def maxpool3x3s2(x):
     y = torch.empty(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, dtype=torch.float32, device=x.device)
     _lib.check(lib.far_maxpool3x3s2_nhwc_f32(_p(x, torch.float32), N, H, W, C, _p(y), _stream()), 'far_maxpool3x3s2_nhwc_f32')
     return y
+
+def stem_conv_rgb(images, pack):
+    """K27.  images (N, 3, H, W) fp32 contiguous on the GPU, as the network consumes them (no flip, no normalisation, no resize) ->
+    relu(bn(conv7x7 stride 2 pad 3)) as NHWC (N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64) for a PackedStemRGB (K25's weight image);
+    `images` is only read.  Takes part in the activation-range guard as K9 does: the pixels are split around the thread's activation
+    exponent, one beyond its range ORs ops.overflow_flag."""
+    lib = _lib.load()
+    if not isinstance(pack, PackedStemRGB):
+        raise _lib.FarHipError('stem_conv_rgb takes a PackedStemRGB')
+    if not images.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if images.dim() != 4 or images.shape[1] != 3 or images.shape[2] < 1 or images.shape[3] < 1:
+        raise _lib.FarHipError(f'stem_conv_rgb expects (N, 3, H, W) images, got {tuple(images.shape)}')
+    N, _, H, W = images.shape
+    y = torch.empty(N, (H - 1) // 2 + 1, (W - 1) // 2 + 1, 64, dtype=torch.float32, device=images.device)
+    rc = lib.far_stem_conv_rgb_f16s(_p(images, torch.float32), N, H, W, _p(pack.packed), _p(pack.scale), _p(pack.shift), _p(y),
+                                    activation_exponent_value(), overflow_flag(images.device).data_ptr(), _stream())
+    _lib.check(rc, 'far_stem_conv_rgb_f16s')
+    return y
+
+def upsample2x_pad(lo=None, skip=None, size=None):
+    """K28, one launch.  lo (N, h, w, C) fp32 NHWC -> F.interpolate(lo, scale_factor=2, mode='bilinear', align_corners=True) as
+    (N, 2h, 2w, C); skip (N, hs, ws, Cs) -> the skip map zero-padded to (N, 2h, 2w, Cs), diff // 2 before and the rest after
+    (resunet.py:90-95).  Returns (up, padded); an absent input gives None (size = (2h, 2w) is then needed for the pad alone); a skip
+    map that already has the size is returned as it is."""
+    lib = _lib.load()
+    if lo is None and skip is None:
+        raise _lib.FarHipError('upsample2x_pad: nothing to do')
+    for t in (lo, skip):
+        if t is not None and not t.is_cuda:
+            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+        if t is not None and (t.dim() != 4 or t.shape[-1] % 4 or t.dtype != torch.float32):
+            raise _lib.FarHipError(f'upsample2x_pad expects fp32 NHWC (N, H, W, C) with C % 4 == 0, got {tuple(t.shape)} {t.dtype}')
+    if lo is not None:
+        N, h, w, C = lo.shape
+        if size is not None and tuple(size) != (2 * h, 2 * w):
+            raise _lib.FarHipError(f'upsample2x_pad: size {tuple(size)} is not twice {(h, w)}')
+    else:
+        if size is None or size[0] % 2 or size[1] % 2:
+            raise _lib.FarHipError('upsample2x_pad: the pad alone needs an even size = (H, W)')
+        N, h, w, C = skip.shape[0], size[0] // 2, size[1] // 2, 0
+    H, W = 2 * h, 2 * w
+    up = None if lo is None else torch.empty(N, H, W, C, dtype=torch.float32, device=lo.device)
+    padded = None
+    if skip is not None:
+        if skip.shape[0] != N or skip.shape[1] > H or skip.shape[2] > W or skip.shape[1] < 1 or skip.shape[2] < 1:
+            raise _lib.FarHipError(f'upsample2x_pad: a skip map {tuple(skip.shape)} does not fit into ({N}, {H}, {W}, .)')
+        if tuple(skip.shape[1:3]) == (H, W):
+            padded, skip = skip, None                         # nothing to pad: K9 reads the skip map itself
+        else:
+            padded = torch.empty(N, H, W, skip.shape[3], dtype=torch.float32, device=skip.device)
+    if lo is None and skip is None:
+        return up, padded
+    rc = lib.far_upsample2x_pad_f32(_p(lo, torch.float32), N, h, w, C, _p(up), _p(skip, torch.float32),
+                                    0 if skip is None else skip.shape[1], 0 if skip is None else skip.shape[2],
+                                    0 if skip is None else skip.shape[3], _p(padded) if skip is not None else None, _stream())
+    _lib.check(rc, 'far_upsample2x_pad_f32')
+    return up, padded
+
+def elu(x, inplace=False):
+    """K28.  F.elu(x) (alpha 1) for a contiguous fp32 GPU tensor of any shape; exact fp32 (expm1)."""
+    lib = _lib.load()
+    if not x.is_cuda:
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    y = x if inplace else torch.empty_like(x)
+    _lib.check(lib.far_elu_f32(_p(x, torch.float32), x.numel(), _p(y), _stream()), 'far_elu_f32')
+    return _written(y) if inplace else y

@@ -236,8 +236,10 @@ def corr_volume_warp(vol0, vol1):
         _CVW_GRID[key] = torch.stack([uu, vv], 0).reshape(2, H * W).contiguous()
     agg = torch.empty(B, 2 * D + 3, H, W, dtype=torch.float32, device=vol0.device)
     ws = _ws(lib.far_corr_volume_warp_workspace_bytes(B, H * W), vol0.device)
-    rc = lib.far_corr_volume_warp_f32(_p(vol0.float().contiguous(), torch.float32), _p(vol1.float().contiguous(), torch.float32),
-                                      _p(_CVW_GRID[key]), B, D, H * W, _p(agg), _p(ws), _stream())
+    # (named, not temporaries: a copy made here must stay alive until the launch -- freed at once, the second copy may take its memory)
+    v0, v1 = vol0.float().contiguous(), vol1.float().contiguous()
+    rc = lib.far_corr_volume_warp_f32(_p(v0, torch.float32), _p(v1, torch.float32), _p(_CVW_GRID[key]), B, D, H * W, _p(agg), _p(ws),
+                                      _stream())
     _lib.check(rc, 'far_corr_volume_warp_f32')
     return agg
 

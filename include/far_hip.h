@@ -848,6 +848,26 @@ int far_stem_rgb_f16s(const float* img, long N, int H, int W, const int* rowidx,
 int far_maxpool3x3s2_nhwc_f32(const float* x, long N, int H, int W, int C, float* y, far_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------------
+ * K27  RGB stem of the Map-free regressor's ResUNet encoder at any image size; K28  the decoder's glue (exact fp32, NHWC)
+ * far_stem_conv_rgb_f16s replaces mapfree_6dreg/lib/models/regression/encoder/resunet.py:106-108 (firstconv 7x7 stride 2 pad 3,
+ *   firstbn folded, relu):  y[n][oy][ox][co] = relu(scale[co] 2^(4-act_exp) sum_{c,ky,kx} X[n][c][2 oy+ky-3][2 ox+kx-3] w[co][c][ky][kx]
+ *   + shift[co]), X = img inside the image, 0 outside.  img [N][3][H][W] fp32, not modified; packed / scale: K25's image and scale
+ *   vector (far_stem_rgb_pack_f32); y [N][(H-1)/2+1][(W-1)/2+1][64] NHWC.  Split-fp16 MFMAs; act_exp / overflow as
+ *   far_conv_nhwc_f32 (pixels are split around 2^act_exp; the device int is OR-ed with 1 when one left the range).  Deterministic;
+ *   image n's output does not depend on N.
+ * far_upsample2x_pad_f32 replaces resunet.py:37-39 (F.interpolate(scale_factor=2, bilinear, align_corners=True)) and :90-95
+ *   (skipconnect's F.pad) in one launch: up [N][2h][2w][C] from lo [N][h][w][C]; skip_out [N][2h][2w][Cs] = skip [N][hs][ws][Cs]
+ *   centred ((2h-hs)/2 rows above, (2w-ws)/2 columns left, the rest after) in zeros.  C % 4 == 0, Cs % 4 == 0, hs <= 2h, ws <= 2w,
+ *   16-byte aligned; either half may be absent (both of its pointers NULL).  K9 then reads cat([up, skip_out]) in place (x, x2).
+ * far_elu_f32 replaces resunet.py:26 (F.elu): y[i] = x[i] > 0 ? x[i] : expm1(x[i]); y may be x.
+ * --------------------------------------------------------------------------------------------------- */
+int far_stem_conv_rgb_f16s(const float* img, long N, int H, int W, const void* packed, const float* scale, const float* shift,
+                           float* y, int act_exp, int* overflow, far_stream_t stream);
+int far_upsample2x_pad_f32(const float* lo, long N, int h, int w, int C, float* up, const float* skip, int hs, int ws, int Cs,
+                           float* skip_out, far_stream_t stream);
+int far_elu_f32(const float* x, long n, float* y, far_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------
  * K11  per-pair arithmetic between the solver and the regression head (one launch each)
  * far_pose_pack_f64 replaces src/loftr/utils/supervision.py:218-233 (spvs_RT: [R | t] with the identity fallback of
  *   :221-224, E with its identity fallback, the count tensors) and src/utils/metrics.py:83-85 (< 5 matches: counts 0).
