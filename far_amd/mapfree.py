@@ -267,6 +267,34 @@ def _get(node, name, default=None):
     return getattr(node, name, default) if node is not None else default
 
 
+def _check_aggregator_options(agg, who):
+    """K12 is the aggregator of the FAR configuration only: every other option of aggregator.py:10-17 is refused by name."""
+    on = [k for k in ('POSITION_ENCODER_IM1', 'NORMALISE_DOT', 'RESIDUAL_ATT', 'CV_OUTLAYERS', 'CV_HALF_CHANNELS', 'UPSAMPLE_POS_ENC',
+                      'DUSTBIN') if _get(agg, k)]
+    off = [k for k in ('POSITION_ENCODER', 'MAX_SCORE_CHANNEL') if not _get(agg, k)]
+    if on or off:
+        raise NotImplementedError(f'{who}: K12 (far_corr_volume_warp_f32) is CorrelationVolumeWarping with POSITION_ENCODER and '
+                                  f'MAX_SCORE_CHANNEL and nothing else; not built: {[k + " on" for k in on] + [k + " off" for k in off]}')
+
+
+class CorrelationVolumeWarping(nn.Module):
+    """lib/models/regression/aggregator.py:6-116 in the FAR configuration, trainable: cfg is the reference's AGGREGATOR node
+    (POSITION_ENCODER and MAX_SCORE_CHANNEL on, everything else off), volume_channels must be 32.  No parameters, an empty state
+    dict, num_out_layers = 67.  forward(vol0, vol1): (B, 32, H, W) x 2 on the GPU -> (B, 67, H, W); K12's training forward with its
+    HIP backward (ops.corr_volume_warp_train) when a gradient is needed, the inference launch otherwise -- the same bits either way."""
+
+    def __init__(self, cfg, volume_channels):
+        super().__init__()
+        _check_aggregator_options(cfg, 'CorrelationVolumeWarping')
+        if volume_channels != 32:
+            raise NotImplementedError(f'CorrelationVolumeWarping: K12 is built for 32 volume channels, got {volume_channels!r}')
+        self.position_encoder, self.max_score_channel = True, True
+        self.num_out_layers = 2 * volume_channels + 2 + 1
+
+    def forward(self, vol0, vol1):
+        return ops.corr_volume_warp_train(vol0, vol1)
+
+
 class RegressionModel(nn.Module):
     """lib/models/regression/model.py:33-308, inference.  cfg: the reference's configuration as any attribute tree (a yacs node, the
     namespace of tests/mapfree_reg_inputs.py: ENCODER / AGGREGATOR / HEAD / TRAINING / SOLVER); matcher: a far_amd.loftr.LoFTR
@@ -331,12 +359,7 @@ class RegressionModel(nn.Module):
                      f"{_get(enc, 'NOT_CONCAT')!r}, NUM_OUT_LAYERS {_get(enc, 'NUM_OUT_LAYERS')!r}")
         if _get(agg, 'TYPE') != 'CorrelationVolumeWarping':
             raise no(f"RegressionModel: aggregator {_get(agg, 'TYPE')!r} is not built (only 'CorrelationVolumeWarping', K12)")
-        on = [k for k in ('POSITION_ENCODER_IM1', 'NORMALISE_DOT', 'RESIDUAL_ATT', 'CV_OUTLAYERS', 'CV_HALF_CHANNELS', 'UPSAMPLE_POS_ENC',
-                          'DUSTBIN') if _get(agg, k)]
-        off = [k for k in ('POSITION_ENCODER', 'MAX_SCORE_CHANNEL') if not _get(agg, k)]
-        if on or off:
-            raise no('RegressionModel: K12 (far_corr_volume_warp_f32) is CorrelationVolumeWarping with POSITION_ENCODER and '
-                     f'MAX_SCORE_CHANNEL and nothing else; not built: {[k + " on" for k in on] + [k + " off" for k in off]}')
+        _check_aggregator_options(agg, 'RegressionModel')
         if _get(head, 'TYPE') != 'DirectDeepResBlockMLP':
             raise no(f"RegressionModel: head {_get(head, 'TYPE')!r} is not built (only 'DirectDeepResBlockMLP')")
         if not _get(head, 'BATCH_NORM', True):

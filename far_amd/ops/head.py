@@ -221,6 +221,16 @@ def pose_features(rt, counts=()):
 
 _CVW_GRID = {}
 
+def _cvw_grid(H, W, device):
+    """(2, H W) meshgrid of linspace(-1, 1, H) x linspace(-1, 1, W) (aggregator.py:81-84), cached per grid and device."""
+    key = (H, W, str(device))
+    if key not in _CVW_GRID:
+        u = torch.linspace(-1, 1, H, device=device)
+        v = torch.linspace(-1, 1, W, device=device)
+        uu, vv = torch.meshgrid(u, v, indexing='ij')
+        _CVW_GRID[key] = torch.stack([uu, vv], 0).reshape(2, H * W).contiguous()
+    return _CVW_GRID[key]
+
 def corr_volume_warp(vol0, vol1):
     """K12.  vol0, vol1 (B, 32, H, W) fp32 -> agg (B, 67, H, W) = cat[vol0, warped vol1, warped (u, v) grid, max score]:
     CorrelationVolumeWarping.forward of the Map-free 6DReg model (aggregator.py:44-115) without the (B, HW, HW) volume."""
@@ -228,20 +238,83 @@ def corr_volume_warp(vol0, vol1):
     B, D, H, W = vol0.shape
     if vol1.shape != vol0.shape:
         raise _lib.FarHipError('Feature volumes shape must match')
-    key = (H, W, str(vol0.device))
-    if key not in _CVW_GRID:
-        u = torch.linspace(-1, 1, H, device=vol0.device)
-        v = torch.linspace(-1, 1, W, device=vol0.device)
-        uu, vv = torch.meshgrid(u, v, indexing='ij')
-        _CVW_GRID[key] = torch.stack([uu, vv], 0).reshape(2, H * W).contiguous()
+    grid = _cvw_grid(H, W, vol0.device)
     agg = torch.empty(B, 2 * D + 3, H, W, dtype=torch.float32, device=vol0.device)
     ws = _ws(lib.far_corr_volume_warp_workspace_bytes(B, H * W), vol0.device)
     # (named, not temporaries: a copy made here must stay alive until the launch -- freed at once, the second copy may take its memory)
     v0, v1 = vol0.float().contiguous(), vol1.float().contiguous()
-    rc = lib.far_corr_volume_warp_f32(_p(v0, torch.float32), _p(v1, torch.float32), _p(_CVW_GRID[key]), B, D, H * W, _p(agg), _p(ws),
+    rc = lib.far_corr_volume_warp_f32(_p(v0, torch.float32), _p(v1, torch.float32), _p(grid), B, D, H * W, _p(agg), _p(ws),
                                       _stream())
     _lib.check(rc, 'far_corr_volume_warp_f32')
     return agg
+
+def _cvw_train_fwd(v0, v1):
+    """far_corr_volume_warp_train_f32 on contiguous fp32 volumes -> agg (the bits of corr_volume_warp), saved (row statistics + arg-max)."""
+    lib = _lib.load()
+    B, D, H, W = v0.shape
+    if v1.shape != v0.shape:
+        raise _lib.FarHipError('Feature volumes shape must match')
+    agg = torch.empty(B, 2 * D + 3, H, W, dtype=torch.float32, device=v0.device)
+    saved = _ws(lib.far_corr_volume_warp_train_saved_bytes(B, H * W), v0.device)
+    rc = lib.far_corr_volume_warp_train_f32(_p(v0, torch.float32), _p(v1, torch.float32), _p(_cvw_grid(H, W, v0.device)), B, D, H * W,
+                                            _p(agg), _p(saved), _stream())
+    _lib.check(rc, 'far_corr_volume_warp_train_f32')
+    return agg, saved
+
+def corr_volume_warp_bwd(vol0, vol1, agg, saved, dagg, want=(True, True)):
+    """K12 backward.  vol0, vol1 (B, 32, H, W) fp32, agg and saved as the training forward left them, dagg (B, 67, H, W) in any memory
+    layout (made contiguous NCHW once) -> (dvol0, dvol1), None where `want` is False: that kernel does not run.  Recomputes the
+    softmax tile by tile from the saved row statistics: no (B, HW, HW) tensor, no atomics, the same bits in every run."""
+    lib = _lib.load()
+    B, D, H, W = vol0.shape
+    if vol1.shape != vol0.shape:
+        raise _lib.FarHipError('Feature volumes shape must match')
+    if tuple(dagg.shape) != (B, 2 * D + 3, H, W) or tuple(agg.shape) != (B, 2 * D + 3, H, W):
+        raise _lib.FarHipError(f'corr_volume_warp_bwd: agg and dagg must be {(B, 2 * D + 3, H, W)}, got {tuple(agg.shape)} and {tuple(dagg.shape)}')
+    for t in (vol0, vol1, agg, saved, dagg):
+        if not t.is_cuda:
+            raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if saved.numel() * saved.element_size() < lib.far_corr_volume_warp_train_saved_bytes(B, H * W):
+        raise _lib.FarHipError('corr_volume_warp_bwd: `saved` is smaller than far_corr_volume_warp_train_saved_bytes(B, HW)')
+    v0, v1 = vol0.detach().float().contiguous(), vol1.detach().float().contiguous()
+    g = dagg.detach().float().contiguous()
+    d0 = torch.empty_like(v0) if want[0] else None
+    d1 = torch.empty_like(v1) if want[1] else None
+    if d0 is None and d1 is None:
+        return None, None
+    ws = _ws(lib.far_corr_volume_warp_bwd_workspace_bytes(B, H * W), v0.device)
+    rc = lib.far_corr_volume_warp_bwd_f32(_p(v0, torch.float32), _p(v1, torch.float32), _p(_cvw_grid(H, W, v0.device)),
+                                          _p(agg.detach(), torch.float32), _p(saved), _p(g, torch.float32), B, D, H * W, _p(d0), _p(d1),
+                                          _p(ws), _stream())
+    _lib.check(rc, 'far_corr_volume_warp_bwd_f32')
+    return d0, d1
+
+class _CorrVolumeWarpFn(torch.autograd.Function):
+    """K12 with its HIP backward (corr_volume_warp_bwd_f32.hip), once differentiable."""
+
+    @staticmethod
+    def forward(ctx, vol0, vol1):
+        v0, v1 = vol0.detach().float().contiguous(), vol1.detach().float().contiguous()
+        agg, saved = _cvw_train_fwd(v0, v1)
+        ctx.save_for_backward(v0, v1, agg, saved)
+        ctx.dtypes = (vol0.dtype, vol1.dtype)
+        return agg
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dagg):
+        v0, v1, agg, saved = ctx.saved_tensors
+        d0, d1 = corr_volume_warp_bwd(v0, v1, agg, saved, dagg, want=ctx.needs_input_grad[:2])
+        return (None if d0 is None else d0.to(ctx.dtypes[0])), (None if d1 is None else d1.to(ctx.dtypes[1]))
+
+def corr_volume_warp_train(vol0, vol1):
+    """K12 with gradients: the bits of corr_volume_warp(vol0, vol1), differentiable once in both volumes (only the gradients autograd asks
+    for are computed).  Under torch.no_grad(), or when neither volume requires a gradient, it is the inference launch."""
+    if not (vol0.is_cuda and vol1.is_cuda):
+        raise _lib.FarHipError('far_amd ops need tensors on the GPU (no CPU fallback exists)')
+    if not (torch.is_grad_enabled() and (vol0.requires_grad or vol1.requires_grad)):
+        return corr_volume_warp(vol0, vol1)
+    return _CorrVolumeWarpFn.apply(vol0, vol1)
 
 # ---------------------------------------------------------------------------------------------------------------------
 # K15: row-independent exact-fp32 layers of the regression head (head_linear_f32.hip)

@@ -980,6 +980,20 @@ size_t far_corr_volume_warp_workspace_bytes(int B, int HW);
 int far_corr_volume_warp_f32(const float* vol0, const float* vol1, const float* grid, int B, int D, int HW, float* agg,
                              void* ws, far_stream_t stream);
 
+/* K12 training (corr_volume_warp_bwd_f32.hip): no (HW, HW) tensor in either direction, exact fp32, no atomics (the same bits from run
+ * to run, and for a pair alone or inside a batch).
+ * far_corr_volume_warp_train_f32 = far_corr_volume_warp_f32 (the same bits in agg) that also keeps, per row, the log2-domain maximum,
+ *   the sum and the arg-max column j* (lowest index among equal scores) in the caller-owned `saved`
+ *   (far_corr_volume_warp_train_saved_bytes(B, HW): no GPU needed).
+ * far_corr_volume_warp_bwd_f32: dagg [B][2 D + 3][HW] (contiguous) -> dvol0, dvol1 [B][D][HW]; either may be NULL and its kernel is
+ *   skipped.  agg and saved are the training forward's; ws: far_corr_volume_warp_bwd_workspace_bytes(B, HW). */
+size_t far_corr_volume_warp_train_saved_bytes(int B, int HW);
+size_t far_corr_volume_warp_bwd_workspace_bytes(int B, int HW);
+int far_corr_volume_warp_train_f32(const float* vol0, const float* vol1, const float* grid, int B, int D, int HW, float* agg,
+                                   void* saved, far_stream_t stream);
+int far_corr_volume_warp_bwd_f32(const float* vol0, const float* vol1, const float* grid, const float* agg, const void* saved,
+                                 const float* dagg, int B, int D, int HW, float* dvol0, float* dvol1, void* ws, far_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
